@@ -9,7 +9,7 @@ Hp = 20, batch = 1024 noise seeds.  With N GPUs each rank solves its own 1024
 problems (global problem indices rank*1024 ...), no collective on the data
 path ("weak" scaling); only a barrier and a max-reduction of the time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \\
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -17,9 +17,15 @@ Without a launcher (no WORLD_SIZE in the environment), ``--gpus N`` with N > 1
 starts the N rank processes itself, one per GPU, before anything touches a GPU
 (spawn_ranks), and exits with the worst rank's return code.
 
-Prints ONE JSON line (rank 0).  ``roofline`` prices the dominant (only)
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps
+and prints the headline figures (``value``, ``ms_per_step``) of the workload.
+``--dump-outputs DIR`` also writes the SolveResult arrays of the last timed step
+as DIR/<name>.npy (float64; the inputs are seeded, so two builds of the library
+can be compared output for output).  Everything else is measured only with
+``--full``: ``roofline`` prices the dominant (only)
 kernel against the FP64 peak with the algorithmic FLOP count of the executed
-algorithm (scpqp/flops.py); ``cpu_baseline`` times the in-repo CPU
+algorithm (scpqp/flops.py); ``e2e_solves_per_s`` is the host-to-host rate; the
+iteration statistics; ``cpu_baseline`` times the in-repo CPU
 restatement of the reference path (oracle/: faithful mode = the reference CPU
 path, and structured mode = the optimised CPU path, each at the all-core and the
 1-core rate) on a bounded sample of the same problems on the host cores, and
@@ -201,6 +207,38 @@ def host_cores():
     return max(1, min(n, int(os.environ.get("SCPQP_CPU_WORKERS", "16"))))
 
 
+# ----------------------------------------------------------------------------- outputs
+DUMP_FIELDS = ("u", "traj", "status", "n_scp", "n_ipm", "obj", "max_violation", "sum_violations",
+               "feasible", "n_polish", "n_refine", "n_warm")
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_rows(B, bytes_per_problem, limit=DUMP_MAX_BYTES):
+    """Problems of the batch that --dump-outputs writes: all of them, or, where the arrays
+    would exceed `limit` bytes, a fixed seeded sample of as many as fit (sorted indices)."""
+    keep = limit // max(bytes_per_problem, 1)
+    if keep >= B:
+        return np.arange(B)
+    return np.sort(np.random.Generator(np.random.PCG64(0)).choice(B, size=keep, replace=False))
+
+
+def dump_outputs(out, dirname, rank=0):
+    """Write the SolveResult a caller of ScpQpSolver.solve receives as <dirname>/<name>.npy,
+    every array as float64 with the problem index first (``rows.npy``: the problems
+    written).  Ranks above 0 write <name>.rank<r>.npy.  Returns {name: shape}."""
+    arrays = {k: getattr(out, k).cpu().numpy() for k in DUMP_FIELDS}
+    B = arrays["u"].shape[0]
+    per_problem = 8 * (1 + sum(a[0].size for a in arrays.values())) if B else 0
+    rows = dump_rows(B, per_problem)
+    arrays = {k: a[rows] for k, a in arrays.items()}
+    arrays["rows"] = rows
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f".rank{rank}" if rank else ""
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, f"{k}{sfx}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 # ----------------------------------------------------------------------------- ranks
 def spawn_ranks(n, cpu_path=None):
     """``bench.py --gpus N`` run directly: start the N ranks as child processes of
@@ -250,7 +288,13 @@ def main():
     ap.add_argument("--n-veh", type=int, default=4)
     ap.add_argument("--hp", type=int, default=20)
     ap.add_argument("--cpu-sample", type=int, default=512)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline "
+                         "and trajectory parity sample (unless --no-cpu), the end-to-end leg, "
+                         "the roofline block and the iteration statistics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's SolveResult arrays as DIR/<name>.npy")
     ap.add_argument("--config", choices=("c2", "c3", "c4", "c5"), default="c2",
                     help="BASELINE config: c2 4 veh Hp 20 B 1024 (the metric's workload, default); "
                          "c3 8 veh Hp 30 B 4096; c4 4 veh Hp 20, 65536 problems as 8192 per "
@@ -258,6 +302,9 @@ def main():
     ap.add_argument("--lib", default=None,
                     help="tools only: another build of the library (A/B runs, tools/gpu.sh ab)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    with_cpu = args.full and not args.no_cpu
     mixed = None
     if args.config == "c4":
         # BASELINE configs[3]: 4 vehicles x 65536 Monte-Carlo realisations, Hp 20, sharded
@@ -277,7 +324,6 @@ def main():
     if world != args.gpus and world > 1:
         print(f"warning: WORLD_SIZE={world} != --gpus {args.gpus}", file=sys.stderr)
 
-    from scpqp import flops as FL
     from scpqp import shard
     import Scenarios  # the drop-in scenario module (host logic)
 
@@ -288,14 +334,14 @@ def main():
     B = args.batch
     bt = shard.shard_batch(sc, B, rank, base_seed=0, mixed_hp=mixed)
 
-    # CPU baseline first, at every N, before any process of the run touches the GPU:
+    # --full: CPU baseline first, at every N, before any process of the run touches the GPU:
     # bench.py --gpus N run directly times it in the parent (which never initialises the
     # GPU) on rank 0's shard and hands it to rank 0; under an external launcher rank 0
     # times it itself before its first GPU call (the other ranks wait in the rendezvous)
     cpu = None
     if spawner:
         path = None
-        if not args.no_cpu:
+        if with_cpu:
             import tempfile
             cpu = cpu_leg(bt, args.n_veh, args.cpu_sample, B)
             fd, path = tempfile.mkstemp(prefix="scpqp_cpu_", suffix=".json")
@@ -307,7 +353,7 @@ def main():
             if path:
                 os.unlink(path)
         sys.exit(rc)
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and with_cpu:
         if os.environ.get("SCPQP_CPU_RESULT"):
             cpu = cpu_leg_load(os.environ["SCPQP_CPU_RESULT"])
         else:
@@ -365,10 +411,57 @@ def main():
     kern_ms_median = float(np.median(step_ms)) if step_ms else kern_ms
     elapsed = shard.max_over_ranks(elapsed, dist, dev)
 
+    line = {
+        "metric": METRIC,
+        "value": world * B * args.steps / elapsed,
+        "unit": "SCP solves/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "ms_per_step_median": shard.max_over_ranks(kern_ms_median * 1e-3, dist, dev) * 1e3,
+        "ms_per_step_note": "ms_per_step: the K timed steps' wall time / K (max over ranks); "
+                            "ms_per_step_median: median of the per-step HIP-event times on the "
+                            "launch stream (max over ranks)",
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (circle scenario x0 + N(0,diag(.05,.05,.005,.02,0,.002)^2), Ec noise N(0,3e-6^2))",
+        "config": {"workload": f"{args.config}: {args.n_veh}-vehicle circle/crossing, "
+                               f"Hp={'{10,20,30} mixed' if mixed else args.hp}, "
+                               f"batch={B} noise seeds per GPU, full SCP solve per problem",
+                   "n_veh": args.n_veh, "hp": list(mixed) if mixed else args.hp, "batch_per_gpu": B,
+                   "parallelism": (f"{world} of 8 shards of c4's 65536 problems (8192 per rank, "
+                                   f"no collective)" if args.config == "c4" else
+                                   f"{world} independent shards (no collective)")},
+    }
+    if args.dump_outputs:
+        # before --full runs the solver again: what the last timed step left in `out`
+        shapes = dump_outputs(out, args.dump_outputs, rank)
+        line["outputs"] = {"dir": args.dump_outputs, "dtype": "float64", "shapes": shapes}
+    if args.full:
+        ins = (x0, u0, ec) + ((hpt,) if mixed else ())
+        line.update(full_figures(args, S, out, bt, mixed, ins, world, B, elapsed, kern_ms, cpu,
+                                 dist, dev))
+    if rank == 0:
+        print(json.dumps(line))
+    if dist:
+        dist.destroy_process_group()
+    S.close()
+
+
+def full_figures(args, S, out, bt, mixed, ins, world, B, elapsed, kern_ms, cpu, dist, dev):
+    """--full: what the run measures beside its headline figure, as further keys of the
+    result line: the end-to-end leg (a few more solves), the iteration statistics, the
+    roofline block and, with a CPU leg, the CPU baseline and the trajectory parity."""
+    import torch
+    from scpqp import flops as FL
+    from scpqp import shard
+
     # end-to-end leg (SURVEY 8d): host (pinned) inputs -> H2D -> solve -> D2H of the result
     # arrays main.py consumes (u, traj, status, obj, max_violation); reported beside `value`,
     # never as it
-    ins = (x0, u0, ec) + ((hpt,) if mixed else ())
     h_in = [t.cpu().pin_memory() for t in ins]
     d_in = [torch.empty_like(t) for t in ins]
     outs = (out.u, out.traj, out.status, out.obj, out.max_violation)
@@ -396,8 +489,6 @@ def main():
     achieved_tf = flops / (kern_ms * 1e-3) / 1e12
     dense = FL.survey_dense_batch(args.n_veh, bt.hp, 0, n_scp, n_ipm)
     dense_tf = dense / (kern_ms * 1e-3) / 1e12
-    ms_per_step = elapsed / args.steps * 1e3
-    value = world * B * args.steps / elapsed
 
     # HBM bytes per launch from the committed rocprofv3 FETCH_SIZE/WRITE_SIZE passes of this
     # workload at its default batch (tools/gpu.sh pmc + tools/pmc_summary.py)
@@ -423,29 +514,6 @@ def main():
     bound, bound_note = roofline_bound(sq, flops)
 
     line = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "SCP solves/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "ms_per_step_median": shard.max_over_ranks(kern_ms_median * 1e-3, dist, dev) * 1e3,
-        "ms_per_step_note": "ms_per_step: the K timed steps' wall time / K (max over ranks); "
-                            "ms_per_step_median: median of the per-step HIP-event times on the "
-                            "launch stream (max over ranks)",
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (circle scenario x0 + N(0,diag(.05,.05,.005,.02,0,.002)^2), Ec noise N(0,3e-6^2))",
-        "config": {"workload": f"{args.config}: {args.n_veh}-vehicle circle/crossing, "
-                               f"Hp={'{10,20,30} mixed' if mixed else args.hp}, "
-                               f"batch={B} noise seeds per GPU, full SCP solve per problem",
-                   "n_veh": args.n_veh, "hp": list(mixed) if mixed else args.hp, "batch_per_gpu": B,
-                   "parallelism": (f"{world} of 8 shards of c4's 65536 problems (8192 per rank, "
-                                   f"no collective)" if args.config == "c4" else
-                                   f"{world} independent shards (no collective)")},
         "roofline": {"bound": bound, "bound_note": bound_note, "achieved": achieved_tf, "peak": FP64_PEAK_TFLOPS,
                      "unit": "TFLOP/s", "frac": achieved_tf / FP64_PEAK_TFLOPS, "traffic": traffic,
                      "kernel": "scp_kernel", "kernel_ms": kern_ms,
@@ -507,11 +575,7 @@ def main():
                                    f"with equal SCP iteration count")
         line["traj_linf_err_capped"] = max(capped) if capped else None
         line["capped_sample"] = f"{len(capped)} problems at the 20-QP cap (not converged)"
-    if rank == 0:
-        print(json.dumps(line))
-    if dist:
-        dist.destroy_process_group()
-    S.close()
+    return line
 
 
 if __name__ == "__main__":

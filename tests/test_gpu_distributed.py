@@ -112,7 +112,7 @@ def test_bench_spawns_ranks_itself(gpu):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT",
                         "SCPQP_DIST_BACKEND")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--cpu-sample", "4", "--batch", "256"]
+           "--warmup", "1", "--full", "--cpu-sample", "4", "--batch", "256"]
     env["SCPQP_CPU_WORKERS"] = "2"
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -214,6 +214,35 @@ def test_bench_cpu_leg_round_trip(tmp_path):
         assert np.array_equal(t0, t1) and n0 == n1 and c0 == c1
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: every SolveResult array as float64 <name>.npy, problem
+    index first; above the size limit a fixed sample of problems, the same on every run."""
+    import types
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    B = 5
+    out = types.SimpleNamespace(**{k: torch.arange(B, dtype=torch.int32) + i
+                                   for i, k in enumerate(bench.DUMP_FIELDS)})
+    out.u = torch.arange(B * 8, dtype=torch.float64).reshape(B, 8) / 3
+    out.traj = torch.arange(B * 8, dtype=torch.float64).reshape(B, 2, 2, 2) / 7
+    shapes = bench.dump_outputs(out, str(tmp_path / "d"))
+    assert set(shapes) == set(bench.DUMP_FIELDS) | {"rows"}
+    for k in bench.DUMP_FIELDS:
+        a = np.load(tmp_path / "d" / f"{k}.npy")
+        assert a.dtype == np.float64 and list(a.shape) == shapes[k] and a.shape[0] == B
+        assert np.array_equal(a, getattr(out, k).numpy())
+    assert np.array_equal(np.load(tmp_path / "d" / "rows.npy"), np.arange(B))
+    bench.dump_outputs(out, str(tmp_path / "d"), rank=1)
+    assert np.array_equal(np.load(tmp_path / "d" / "u.rank1.npy"), out.u.numpy())
+    # the whole batch where it fits; else as many problems as fit, sorted, seeded
+    assert np.array_equal(bench.dump_rows(1024, 2648), np.arange(1024))
+    rows = bench.dump_rows(1000, 100, limit=25000)
+    assert len(rows) == 250 and len(set(rows.tolist())) == 250 and np.all(np.diff(rows) > 0)
+    assert rows.min() >= 0 and rows.max() < 1000
+    assert np.array_equal(rows, bench.dump_rows(1000, 100, limit=25000))
+
+
 def test_bench_cpu_baseline_fields_on_a_sample():
     """SURVEY 8(d)'s CPU leg on a 4-problem c2 sample: the reference CPU path (faithful
     mode) and the structured mode, each at the all-core and the 1-core rate, on the same

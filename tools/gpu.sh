@@ -9,7 +9,7 @@
 #   smoke                 __graft_entry__.smoke()
 #   bench:<cfg>[,steps]   bench.py line of one BASELINE configuration (c2 with the CPU leg)
 #   ab:<cfgs>:<libs>[:reps]  A/B of library builds, e.g. ab:c2/10,c4/3:scpqp/libscpqp.so,/tmp/x.so:2
-#                         (bench.py --no-cpu, alternating; VAR=value@lib.so sets an env var)
+#                         (bench.py --full --no-cpu, alternating; VAR=value@lib.so sets an env var)
 #   phases:[VAR=v@]<lib>[:cfgs]  phase stamps of a -DSCPQP_PROF build (tools/gpu_prof.py), cfgs as 4/20/1
 #   timeline:[VAR=v@]<lib>       per-problem start/end of a -DSCPQP_PROF build (c2, B = 1024)
 #   stats:<cfg>           rocprofv3 --kernel-trace --stats of the bench
@@ -60,7 +60,7 @@ for st in "$@"; do
     bench)
         cfg=${rest%%,*}; steps=""; [ "$cfg" != "$rest" ] && steps="--steps ${rest#*,} --warmup 1"
         extra=""   # every config with its CPU leg and parity sample (verdict r05 item 6)
-        run bench_$cfg 600 python bench.py --config $cfg $steps $extra
+        run bench_$cfg 600 python bench.py --full --config $cfg $steps $extra
         grep '^{' $OUT/bench_$cfg.log > $OUT/bench_$cfg.json
         line $cfg < $OUT/bench_$cfg.json ;;
     ab)
@@ -71,7 +71,7 @@ for st in "$@"; do
                 for ent in ${libs//,/ }; do
                     lib=${ent##*@}; envs=""; [ "$ent" != "$lib" ] && envs=${ent%%@*}
                     [ "${lib:0:1}" = / ] || lib=$PWD/$lib
-                    run ab 300 env $envs python bench.py --lib $lib --no-cpu --config $c --steps $n --warmup 1
+                    run ab 300 env $envs python bench.py --full --lib $lib --no-cpu --config $c --steps $n --warmup 1
                     grep '^{' $OUT/ab.log | line "$c $ent" | tee -a $OUT/ab.txt
                 done
             done
@@ -91,7 +91,7 @@ for st in "$@"; do
         head -20 $OUT/$name.log ;;
     stats)
         c=$rest; steps=5; [ $c = c3 ] && steps=2; [ $c = c2 ] && steps=10
-        run stats_$c 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats_$c -o run -- python3 bench.py --config $c --steps $steps --warmup 2 --no-cpu
+        run stats_$c 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats_$c -o run -- python3 bench.py --full --config $c --steps $steps --warmup 2 --no-cpu
         find $OUT/stats_$c -name '*kernel_stats.csv' -exec cp {} $OUT/kernel_stats_$c.csv \;
         grep '^{' $OUT/stats_$c.log > $OUT/bench_under_rocprof_$c.json || true
         head -3 $OUT/kernel_stats_$c.csv ;;
@@ -99,16 +99,16 @@ for st in "$@"; do
         c=$rest
         timeout -s KILL 60 rocprofv3 -L > $OUT/counters_list.txt 2>&1 || true
         MFMA=$(python tools/pick_counters.py $OUT/counters_list.txt)
-        run sq_$c 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_BUSY_CYCLES -f csv -d $OUT/sq_$c -o run -- python3 bench.py --config $c --steps 2 --warmup 1 --no-cpu
+        run sq_$c 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_BUSY_CYCLES -f csv -d $OUT/sq_$c -o run -- python3 bench.py --full --config $c --steps 2 --warmup 1 --no-cpu
         python tools/pmc_table.py $(find $OUT/sq_$c -name '*counter_collection.csv') > $OUT/pmc_sq_$c.txt
         cat $OUT/pmc_sq_$c.txt
         if [ -n "$MFMA" ]; then
-            run mfma_$c 300 rocprofv3 --kernel-trace --pmc $MFMA -f csv -d $OUT/mfma_$c -o run -- python3 bench.py --config $c --steps 2 --warmup 1 --no-cpu
+            run mfma_$c 300 rocprofv3 --kernel-trace --pmc $MFMA -f csv -d $OUT/mfma_$c -o run -- python3 bench.py --full --config $c --steps 2 --warmup 1 --no-cpu
             python tools/pmc_table.py $(find $OUT/mfma_$c -name '*counter_collection.csv') > $OUT/pmc_mfma_$c.txt
             cat $OUT/pmc_mfma_$c.txt
         fi
-        run fetch_$c 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d $OUT/fetch_$c -o run -- python3 bench.py --config $c --steps 2 --warmup 1 --no-cpu
-        run write_$c 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -f csv -d $OUT/write_$c -o run -- python3 bench.py --config $c --steps 2 --warmup 1 --no-cpu
+        run fetch_$c 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d $OUT/fetch_$c -o run -- python3 bench.py --full --config $c --steps 2 --warmup 1 --no-cpu
+        run write_$c 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -f csv -d $OUT/write_$c -o run -- python3 bench.py --full --config $c --steps 2 --warmup 1 --no-cpu
         f=$(find $OUT/fetch_$c -name '*counter_collection.csv'); w=$(find $OUT/write_$c -name '*counter_collection.csv')
         python tools/pmc_summary.py $f $w $OUT/pmc_traffic_$c.json | grep -E "raw|bytes_per_launch|scratch" ;;
     rollout)

@@ -38,7 +38,7 @@ def main():
         "mfma_f64_flops": 2048.0 * mfma,
         "mfma_busy_cycles_per_inst": busy / mfma if mfma else None,
         "note": (f"rocprofv3 --kernel-trace --pmc, one 8-counter SQ pass and one MFMA/VALU pass, "
-                 f"bench.py --config {cfg} --steps 2 --warmup 1 --no-cpu; per-dispatch means "
+                 f"bench.py --full --config {cfg} --steps 2 --warmup 1 --no-cpu; per-dispatch means "
                  f"(tools/pmc_table.py), shipped library (tools/gpu.sh pmc {tag})"),
     }
     json.dump(rec, sys.stdout, indent=1)

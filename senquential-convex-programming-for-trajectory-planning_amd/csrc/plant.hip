@@ -7,6 +7,10 @@
 //                           (main.py:176-191)
 //   scpqp_clip_controls     steering-limit enforcement of the controller output
 //                           (main.py:164-174)
+//   scpqp_delay_compensate_noisy, scpqp_plant_step_noisy, scpqp_noise_fill
+//                           the same integrators with the reference's model noise
+//                           drawn anew per right-hand-side evaluation
+//                           (include/scpqp_noise.h, Model.py:84-86)
 //
 // The reference integrates with scipy (odeint = LSODA at rtol = atol = 1.49e-8
 // for the delay compensation, dopri5 at rtol = atol = 1e-8 for the plant).
@@ -21,7 +25,8 @@
 
 #include <math.h>
 
-#include "scpqp.h"
+#include "scpqp_noise.h"
+#include "scpqp_philox.h"
 
 int scpqp_fail_(int code, const char* msg);   // scpqp.hip: sets scpqp_last_error()
 
@@ -36,9 +41,11 @@ struct Veh {
 
 // Model.py:61-87 (BicyleModel.ode / odes_): dx for state
 // [x, y, heading, speed (rear axle), acceleration, steering angle].
-// n0, n1: the additive noise of dx[0], dx[1] (Model.py:84-86), held constant
-// over the call (the reference draws it anew per right-hand-side evaluation,
-// and is_noise is False in main.py:235).
+// n0, n1: the additive noise of dx[0], dx[1] (Model.py:84-86).  The reference
+// draws it anew per right-hand-side evaluation: the kNoisy integrators below do
+// the same from the lane's Philox stream (include/scpqp_noise.h) before every
+// call.  The entry points of scpqp.h hold the caller's pair constant over the
+// call instead (zero when noise is NULL; is_noise is False in main.py:235).
 __device__ __forceinline__ void bicycle(const double (&x)[NX], const Veh& p, double (&dx)[NX]) {
     const double L = p.lf + p.lr, R = p.lr / L;
     const double tu = tan(x[5]);
@@ -52,26 +59,36 @@ __device__ __forceinline__ void bicycle(const double (&x)[NX], const Veh& p, dou
     dx[5] = (p.uref - x[5]) / 0.1;
 }
 
-__device__ __forceinline__ void rk4(double (&x)[NX], const Veh& p, double h) {
+using scpqp_noise_dev::Stream;
+
+// kNoisy: p.n0, p.n1 are redrawn before each of the four evaluations (c0 order
+// k1, k2, k3, k4); else p is left as it is and ns is unused
+template <bool kNoisy>
+__device__ __forceinline__ void rk4(double (&x)[NX], Veh& p, double h, Stream& ns) {
     double k1[NX], k2[NX], k3[NX], k4[NX], y[NX];
+    if constexpr (kNoisy) scpqp_noise_dev::draw(ns, p.n0, p.n1);
     bicycle(x, p, k1);
 #pragma unroll
     for (int i = 0; i < NX; ++i) y[i] = x[i] + 0.5 * h * k1[i];
+    if constexpr (kNoisy) scpqp_noise_dev::draw(ns, p.n0, p.n1);
     bicycle(y, p, k2);
 #pragma unroll
     for (int i = 0; i < NX; ++i) y[i] = x[i] + 0.5 * h * k2[i];
+    if constexpr (kNoisy) scpqp_noise_dev::draw(ns, p.n0, p.n1);
     bicycle(y, p, k3);
 #pragma unroll
     for (int i = 0; i < NX; ++i) y[i] = x[i] + h * k3[i];
+    if constexpr (kNoisy) scpqp_noise_dev::draw(ns, p.n0, p.n1);
     bicycle(y, p, k4);
 #pragma unroll
     for (int i = 0; i < NX; ++i) x[i] += h / 6.0 * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]);
 }
 
 // integrate x over a span of length T with n equal RK4 steps
-__device__ __forceinline__ void flow(double (&x)[NX], const Veh& p, double T, int n) {
+template <bool kNoisy>
+__device__ __forceinline__ void flow(double (&x)[NX], Veh& p, double T, int n, Stream& ns) {
     const double h = T / n;
-    for (int s = 0; s < n; ++s) rk4(x, p, h);
+    for (int s = 0; s < n; ++s) rk4<kNoisy>(x, p, h, ns);
 }
 
 __device__ __forceinline__ int steps_for(double T, double hmax) {
@@ -79,23 +96,30 @@ __device__ __forceinline__ int steps_for(double T, double hmax) {
     return n < 1 ? 1 : n;
 }
 
-// one lane per (problem, vehicle): linspace(0, horizon, n_out) outputs
-__global__ __launch_bounds__(PT) void delay_kernel(scpqp_plant_params p, int B, double horizon,
-                                                   int n_out, double hmax, const double* x_meas,
-                                                   const double* u_hold, const double* noise,
-                                                   double* x0_out, double* traj_out) {
+// one lane per (problem, vehicle): linspace(0, horizon, n_out) outputs.  kNoisy:
+// site 0 stream of (b_offset + b, v), counting on across the n_out - 1 spans.
+template <bool kNoisy>
+__device__ __forceinline__ void delay_lane(const scpqp_plant_params& p, int B, double horizon,
+                                           int n_out, double hmax, const double* x_meas,
+                                           const double* u_hold, const double* noise,
+                                           const scpqp_noise& nz, double* x0_out,
+                                           double* traj_out) {
     const int V = p.n_veh;
     const int g = blockIdx.x * PT + threadIdx.x;
     if (g >= B * V) return;
     const int b = g / V, v = g % V;
     Veh q{p.lf[v], p.lr[v], u_hold[g], noise ? noise[2 * g] : 0.0, noise ? noise[2 * g + 1] : 0.0};
+    Stream ns{};
+    if constexpr (kNoisy)
+        ns = scpqp_noise_dev::make_stream(nz.seed, nz.sigma, nz.epoch, SCPQP_NOISE_SITE_DELAY, 0u,
+                                          (uint32_t)v, nz.b_offset + (uint32_t)b);
     double x[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) x[i] = x_meas[(size_t)g * NX + i];
     const double span = horizon / (n_out - 1);
     const int n = steps_for(span, hmax);
     for (int j = 0; j < n_out; ++j) {
-        if (j > 0) flow(x, q, span, n);
+        if (j > 0) flow<kNoisy>(x, q, span, n, ns);
         if (traj_out) {
             // MPC_delay_compensation_trajectory layout [n_out][nx][nVeh] per problem
 #pragma unroll
@@ -107,27 +131,77 @@ __global__ __launch_bounds__(PT) void delay_kernel(scpqp_plant_params p, int B, 
     for (int i = 0; i < NX; ++i) x0_out[(size_t)g * NX + i] = x[i];
 }
 
+__global__ __launch_bounds__(PT) void delay_kernel(scpqp_plant_params p, int B, double horizon,
+                                                   int n_out, double hmax, const double* x_meas,
+                                                   const double* u_hold, const double* noise,
+                                                   double* x0_out, double* traj_out) {
+    delay_lane<false>(p, B, horizon, n_out, hmax, x_meas, u_hold, noise, scpqp_noise{}, x0_out,
+                      traj_out);
+}
+
+__global__ __launch_bounds__(PT) void delay_kernel_noisy(scpqp_plant_params p, int B,
+                                                         double horizon, int n_out, double hmax,
+                                                         const double* x_meas,
+                                                         const double* u_hold, scpqp_noise nz,
+                                                         double* x0_out, double* traj_out) {
+    delay_lane<true>(p, B, horizon, n_out, hmax, x_meas, u_hold, nullptr, nz, x0_out, traj_out);
+}
+
 // one lane per (problem, vehicle, output tick k): main.py:186-190 restarts the
-// integration at t0 for every output time t_k, with the control value of tick k
-__global__ __launch_bounds__(PT) void plant_kernel(scpqp_plant_params p, int B, int n_ticks,
-                                                   double tick, double hmax, const double* x_start,
-                                                   const double* u_tick, const double* noise,
-                                                   double* x_path) {
+// integration at t0 for every output time t_k, with the control value of tick k.
+// kNoisy: site 1 stream of (b_offset + b, v, k): every restart has its own noise,
+// as every restart of the reference consumes fresh draws.
+template <bool kNoisy>
+__device__ __forceinline__ void plant_lane(const scpqp_plant_params& p, int B, int n_ticks,
+                                           double tick, double hmax, const double* x_start,
+                                           const double* u_tick, const double* noise,
+                                           const scpqp_noise& nz, double* x_path) {
     const int V = p.n_veh, K = n_ticks + 1;
     const int g = blockIdx.x * PT + threadIdx.x;
     if (g >= B * V * K) return;
     const int k = g % K, bv = g / K, v = bv % V;
     Veh q{p.lf[v], p.lr[v], u_tick[g], noise ? noise[2 * bv] : 0.0,
           noise ? noise[2 * bv + 1] : 0.0};
+    Stream ns{};
+    if constexpr (kNoisy)
+        ns = scpqp_noise_dev::make_stream(nz.seed, nz.sigma, nz.epoch, SCPQP_NOISE_SITE_PLANT,
+                                          (uint32_t)k, (uint32_t)v, nz.b_offset + (uint32_t)(bv / V));
     double x[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) x[i] = x_start[(size_t)bv * NX + i];
     if (k > 0) {
         const double T = k * tick;
-        flow(x, q, T, steps_for(T, hmax));
+        flow<kNoisy>(x, q, T, steps_for(T, hmax), ns);
     }
 #pragma unroll
     for (int i = 0; i < NX; ++i) x_path[(size_t)g * NX + i] = x[i];
+}
+
+__global__ __launch_bounds__(PT) void plant_kernel(scpqp_plant_params p, int B, int n_ticks,
+                                                   double tick, double hmax, const double* x_start,
+                                                   const double* u_tick, const double* noise,
+                                                   double* x_path) {
+    plant_lane<false>(p, B, n_ticks, tick, hmax, x_start, u_tick, noise, scpqp_noise{}, x_path);
+}
+
+__global__ __launch_bounds__(PT) void plant_kernel_noisy(scpqp_plant_params p, int B, int n_ticks,
+                                                         double tick, double hmax,
+                                                         const double* x_start,
+                                                         const double* u_tick, scpqp_noise nz,
+                                                         double* x_path) {
+    plant_lane<true>(p, B, n_ticks, tick, hmax, x_start, u_tick, nullptr, nz, x_path);
+}
+
+// one lane per (problem, vehicle): the first n_eval draws of the (site, k) stream
+__global__ __launch_bounds__(PT) void fill_kernel(scpqp_noise nz, int B, int V, int site, int k,
+                                                  int n_eval, double* out) {
+    const int g = blockIdx.x * PT + threadIdx.x;
+    if (g >= B * V) return;
+    Stream ns = scpqp_noise_dev::make_stream(nz.seed, nz.sigma, nz.epoch, (uint32_t)site,
+                                             (uint32_t)k, (uint32_t)(g % V),
+                                             nz.b_offset + (uint32_t)(g / V));
+    double* o = out + (size_t)g * n_eval * 2;
+    for (int e = 0; e < n_eval; ++e) scpqp_noise_dev::draw(ns, o[2 * e], o[2 * e + 1]);
 }
 
 // one lane per (problem, vehicle): U[0] within +-umax and u0 +- du_lim, then
@@ -157,6 +231,13 @@ int check_params(const scpqp_plant_params* p) {
     if (p->n_veh < 1 || p->n_veh > SCPQP_MAX_VEH) return scpqp_fail_(SCPQP_E_ARG, "n_veh out of range");
     for (int v = 0; v < p->n_veh; ++v)
         if (!(p->lf[v] + p->lr[v] > 0.0)) return scpqp_fail_(SCPQP_E_ARG, "lf + lr must be > 0");
+    return 0;
+}
+
+int check_noise(const scpqp_noise* nz) {
+    if (!nz) return scpqp_fail_(SCPQP_E_ARG, "null noise parameters");
+    if (!(nz->sigma >= 0.0) || isinf(nz->sigma))
+        return scpqp_fail_(SCPQP_E_ARG, "sigma must be finite and >= 0");
     return 0;
 }
 
@@ -199,6 +280,63 @@ int scpqp_plant_step(const scpqp_plant_params* p, int32_t B, int32_t n_ticks, do
     hipLaunchKernelGGL(plant_kernel, dim3((unsigned)((n + PT - 1) / PT)), dim3(PT), 0,
                        static_cast<hipStream_t>(stream), *p, B, n_ticks, tick, h_max, x_start,
                        u_tick, noise, x_path);
+    return launched();
+}
+
+int scpqp_delay_compensate_noisy(const scpqp_plant_params* p, int32_t B, double horizon,
+                                 int32_t n_out, const double* x_meas, const double* u_hold,
+                                 const scpqp_noise* nz, double* x0_out, double* traj_out,
+                                 double h_max, void* stream) {
+    if (int rc = check_params(p)) return rc;
+    if (int rc = check_noise(nz)) return rc;
+    if (B < 0) return scpqp_fail_(SCPQP_E_ARG, "batch size < 0");
+    if (n_out < 2) return scpqp_fail_(SCPQP_E_ARG, "n_out must be >= 2");
+    if (!(horizon >= 0.0) || !(h_max > 0.0)) return scpqp_fail_(SCPQP_E_ARG, "bad horizon / h_max");
+    if (B == 0) return 0;
+    if (!x_meas || !u_hold || !x0_out) return scpqp_fail_(SCPQP_E_ARG, "null array");
+    const long long n = (long long)B * p->n_veh;
+    if (n > 0x7fffffffLL) return scpqp_fail_(SCPQP_E_SIZE, "B * n_veh too large");
+    hipLaunchKernelGGL(delay_kernel_noisy, dim3((unsigned)((n + PT - 1) / PT)), dim3(PT), 0,
+                       static_cast<hipStream_t>(stream), *p, B, horizon, n_out, h_max, x_meas,
+                       u_hold, *nz, x0_out, traj_out);
+    return launched();
+}
+
+int scpqp_plant_step_noisy(const scpqp_plant_params* p, int32_t B, int32_t n_ticks, double tick,
+                           const double* x_start, const double* u_tick, const scpqp_noise* nz,
+                           double* x_path, double h_max, void* stream) {
+    if (int rc = check_params(p)) return rc;
+    if (int rc = check_noise(nz)) return rc;
+    if (B < 0 || n_ticks < 0) return scpqp_fail_(SCPQP_E_ARG, "batch size / n_ticks < 0");
+    if (n_ticks >= SCPQP_NOISE_MAX_TICKS)
+        return scpqp_fail_(SCPQP_E_SIZE, "n_ticks must be < 65536 (16 bits of the counter)");
+    if (!(tick > 0.0) || !(h_max > 0.0)) return scpqp_fail_(SCPQP_E_ARG, "bad tick / h_max");
+    if (B == 0) return 0;
+    if (!x_start || !u_tick || !x_path) return scpqp_fail_(SCPQP_E_ARG, "null array");
+    const long long n = (long long)B * p->n_veh * (n_ticks + 1);
+    if (n > 0x7fffffffLL) return scpqp_fail_(SCPQP_E_SIZE, "B * n_veh * (n_ticks + 1) too large");
+    hipLaunchKernelGGL(plant_kernel_noisy, dim3((unsigned)((n + PT - 1) / PT)), dim3(PT), 0,
+                       static_cast<hipStream_t>(stream), *p, B, n_ticks, tick, h_max, x_start,
+                       u_tick, *nz, x_path);
+    return launched();
+}
+
+int scpqp_noise_fill(const scpqp_noise* nz, int32_t B, int32_t n_veh, int32_t site, int32_t k,
+                     int32_t n_eval, double* out, void* stream) {
+    if (int rc = check_noise(nz)) return rc;
+    if (B < 0 || n_eval < 0) return scpqp_fail_(SCPQP_E_ARG, "batch size / n_eval < 0");
+    if (n_veh < 1 || n_veh > SCPQP_MAX_VEH) return scpqp_fail_(SCPQP_E_ARG, "n_veh out of range");
+    if (site < SCPQP_NOISE_SITE_DELAY || site > SCPQP_NOISE_SITE_LINEARIZE)
+        return scpqp_fail_(SCPQP_E_ARG, "site must be 0, 1 or 2");
+    if (k < 0) return scpqp_fail_(SCPQP_E_ARG, "k < 0");
+    if (k >= SCPQP_NOISE_MAX_TICKS)
+        return scpqp_fail_(SCPQP_E_SIZE, "k must be < 65536 (16 bits of the counter)");
+    const long long n = (long long)B * n_veh;
+    if (n * n_eval * 2 > 0x7fffffffLL) return scpqp_fail_(SCPQP_E_SIZE, "B * n_veh * n_eval too large");
+    if (B == 0 || n_eval == 0) return 0;
+    if (!out) return scpqp_fail_(SCPQP_E_ARG, "null array");
+    hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((n + PT - 1) / PT)), dim3(PT), 0,
+                       static_cast<hipStream_t>(stream), *nz, B, n_veh, site, k, n_eval, out);
     return launched();
 }
 

@@ -1,4 +1,5 @@
-"""ctypes binding of ``include/scpqp.h`` (the C-ABI of the HIP library).
+"""ctypes binding of ``include/scpqp.h`` and ``include/scpqp_noise.h`` (the C-ABI of the
+HIP library).
 
 The shared library ``libscpqp.so`` is built in-tree (``__graft_entry__.build()``
 or ``python -m scpqp.build``).  There is no CPU fallback: if the library or a
@@ -83,6 +84,18 @@ EXPORTS = ("scpqp_create", "scpqp_destroy", "scpqp_last_error", "scpqp_version",
            "scpqp_trace_layout",
            "scpqp_delay_compensate", "scpqp_plant_step", "scpqp_clip_controls")
 
+
+class Noise(C.Structure):
+    """scpqp_noise (include/scpqp_noise.h): seed, sigma and the caller's part of the counter."""
+    _fields_ = [("seed", C.c_uint64), ("sigma", C.c_double), ("epoch", C.c_uint32),
+                ("b_offset", C.c_uint32)]
+
+
+NOISE_SITE_DELAY, NOISE_SITE_PLANT, NOISE_SITE_LINEARIZE = 0, 1, 2
+
+# every symbol include/scpqp_noise.h declares (checked by tests/test_noise_host.py)
+NOISE_EXPORTS = ("scpqp_delay_compensate_noisy", "scpqp_plant_step_noisy", "scpqp_noise_fill")
+
 _lib = None
 
 
@@ -130,6 +143,15 @@ def load(path=None):
     lib.scpqp_clip_controls.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                         V, V, V, V]
     lib.scpqp_clip_controls.restype = C.c_int
+    NP = C.POINTER(Noise)
+    lib.scpqp_delay_compensate_noisy.argtypes = [PP, C.c_int32, C.c_double, C.c_int32, V, V, NP, V,
+                                                 V, C.c_double, V]
+    lib.scpqp_delay_compensate_noisy.restype = C.c_int
+    lib.scpqp_plant_step_noisy.argtypes = [PP, C.c_int32, C.c_int32, C.c_double, V, V, NP, V,
+                                           C.c_double, V]
+    lib.scpqp_plant_step_noisy.restype = C.c_int
+    lib.scpqp_noise_fill.argtypes = [NP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, V, V]
+    lib.scpqp_noise_fill.restype = C.c_int
     if path is None:
         _lib = lib
     return lib

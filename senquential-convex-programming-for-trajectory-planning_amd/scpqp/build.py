@@ -46,7 +46,8 @@ def build_library(force=False, verbose=False, defines=(), out=None, csrc=None):
     srcs = [os.path.join(src_dir, os.path.basename(x)) for x in SRCS]
     ksrc = os.path.join(src_dir, os.path.basename(KERNEL_SRC))
     hdr = os.path.join(src_dir, os.path.basename(HEADER))
-    deps = srcs + [ksrc, hdr, os.path.join(INCLUDE, "scpqp.h"), __file__]
+    deps = srcs + [ksrc, hdr, os.path.join(src_dir, "scpqp_philox.h"),
+                   os.path.join(INCLUDE, "scpqp.h"), os.path.join(INCLUDE, "scpqp_noise.h"), __file__]
     if not force and os.path.exists(out):
         t = os.path.getmtime(out)
         if all(os.path.getmtime(d) <= t for d in deps):

@@ -3,6 +3,10 @@
 ``delay_compensate``  IterClass delay compensation (MPC_Iter.py:24-33)
 ``plant_step``        closed-loop plant simulation of one MPC step (main.py:176-191)
 ``clip_controls``     steering-limit enforcement (main.py:164-174)
+``NoiseStream``       seed, sigma and counter part of the reference's model noise
+                      (Model.py:84-86), drawn on the device per right-hand-side
+                      evaluation (include/scpqp_noise.h); ``rng=`` of the two
+                      integrators, and ``draw_ec_noise`` for the solve's ec_noise
 
 Arrays are torch-ROCm float64 tensors on the GPU; PyTorch only provides the
 memory and the stream.  The reference integrates with scipy (odeint / dopri5);
@@ -21,6 +25,40 @@ from . import _lib as LB
 H_MAX = 2.5e-3
 STEER_TAU = 0.1       # Model.py:83: dx[5] = (u_ref - u) / 0.1
 DELAY_STEPS = 10      # MPC_Iter.py:21: outputs of the delay-compensation trajectory
+
+
+SIGMA_NOISE = 3e-6    # Model.py:85-86: np.random.normal(0, 0.000003)
+
+
+class NoiseStream:
+    """The reference's per-evaluation model noise as a counter-based stream: ``seed`` keys
+    the generator, ``epoch`` is the MPC step index and ``b_offset`` the global index of the
+    call's first realisation (a rank holding realisations [r * per_rank, (r + 1) * per_rank)
+    passes ``b_offset = r * per_rank``), so a realisation's draws do not depend on how the
+    batch is split.  ``at(epoch)`` gives the stream of another step."""
+
+    def __init__(self, seed, sigma=SIGMA_NOISE, epoch=0, b_offset=0):
+        self.seed, self.epoch, self.b_offset = int(seed), int(epoch), int(b_offset)
+        self.sigma = float(sigma)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed must be in [0, 2**64)")
+        if not (0.0 <= self.sigma < float("inf")):
+            raise ValueError("sigma must be finite and >= 0")
+        if not 0 <= self.epoch < 2 ** 32 or not 0 <= self.b_offset < 2 ** 32:
+            raise ValueError("epoch and b_offset must be in [0, 2**32)")
+
+    def at(self, epoch):
+        return NoiseStream(self.seed, self.sigma, epoch, self.b_offset)
+
+    def c_struct(self):
+        return LB.Noise(seed=self.seed, sigma=self.sigma, epoch=self.epoch, b_offset=self.b_offset)
+
+
+def _one_noise_source(noise, rng):
+    if noise is not None and rng is not None:
+        raise ValueError("pass either noise (constant terms) or rng (a NoiseStream), not both")
+    if rng is not None and not isinstance(rng, NoiseStream):
+        raise TypeError("rng must be a NoiseStream")
 
 
 def plant_params(lf, lr):
@@ -50,9 +88,12 @@ def _stream(device):
 
 
 def delay_compensate(params, x_meas, u_hold, horizon, n_out=DELAY_STEPS, noise=None, h_max=H_MAX,
-                     device=None, want_traj=True):
+                     device=None, want_traj=True, rng=None):
     """x_meas [B, nVeh, 6], u_hold [B, nVeh] -> (x0 [B, nVeh, 6],
-    traj [B, n_out, 6, nVeh] or None): MPC_Iter.py:24-33 for every problem."""
+    traj [B, n_out, 6, nVeh] or None): MPC_Iter.py:24-33 for every problem.
+    ``noise`` [B, nVeh, 2]: constant terms of dx[0], dx[1]; ``rng`` (a NoiseStream):
+    the reference's noise, drawn anew per right-hand-side evaluation."""
+    _one_noise_source(noise, rng)
     device = torch.device(device or "cuda")
     lib = LB.load()
     x = _dev(x_meas, device)
@@ -65,16 +106,25 @@ def delay_compensate(params, x_meas, u_hold, horizon, n_out=DELAY_STEPS, noise=N
         raise ValueError("noise must be [B, nVeh, 2]")
     x0 = torch.empty((B, V, 6), dtype=torch.float64, device=device)
     traj = torch.empty((B, n_out, 6, V), dtype=torch.float64, device=device) if want_traj else None
+    if rng is not None:
+        ns = rng.c_struct()
+        LB.check(lib.scpqp_delay_compensate_noisy(C.byref(params), B, float(horizon), int(n_out),
+                                                  _ptr(x), _ptr(u), C.byref(ns), _ptr(x0),
+                                                  _ptr(traj), float(h_max), _stream(device)), lib)
+        return x0, traj
     LB.check(lib.scpqp_delay_compensate(C.byref(params), B, float(horizon), int(n_out), _ptr(x),
                                         _ptr(u), _ptr(nz), _ptr(x0), _ptr(traj), float(h_max),
                                         _stream(device)), lib)
     return x0, traj
 
 
-def plant_step(params, x_start, u_tick, tick, noise=None, h_max=H_MAX, device=None):
+def plant_step(params, x_start, u_tick, tick, noise=None, h_max=H_MAX, device=None, rng=None):
     """x_start [B, nVeh, 6], u_tick [B, nVeh, K] (K = ticks_per_sim + 1) ->
     x_path [B, nVeh, K, 6]: main.py:184-191 (output k integrated from t0 over
-    k ticks with the constant control u_tick[..., k])."""
+    k ticks with the constant control u_tick[..., k]).  ``noise`` / ``rng`` as in
+    delay_compensate; with ``rng`` every output tick k has its own noise stream, as
+    every restart of the reference's integrator consumes fresh draws."""
+    _one_noise_source(noise, rng)
     device = torch.device(device or "cuda")
     lib = LB.load()
     x = _dev(x_start, device)
@@ -85,9 +135,35 @@ def plant_step(params, x_start, u_tick, tick, noise=None, h_max=H_MAX, device=No
         raise ValueError("x_start must be [B, nVeh, 6] and u_tick [B, nVeh, K]")
     nz = None if noise is None else _dev(noise, device)
     out = torch.empty((B, V, K, 6), dtype=torch.float64, device=device)
+    if rng is not None:
+        ns = rng.c_struct()
+        LB.check(lib.scpqp_plant_step_noisy(C.byref(params), B, K - 1, float(tick), _ptr(x),
+                                            _ptr(u), C.byref(ns), _ptr(out), float(h_max),
+                                            _stream(device)), lib)
+        return out
     LB.check(lib.scpqp_plant_step(C.byref(params), B, K - 1, float(tick), _ptr(x), _ptr(u),
                                   _ptr(nz), _ptr(out), float(h_max), _stream(device)), lib)
     return out
+
+
+def noise_fill(rng, B, n_veh, site, k=0, n_eval=1, device=None):
+    """The raw draws of ``rng``: [B, n_veh, n_eval, 2] = sigma * (z0, z1) of evaluations
+    c0 = 0..n_eval-1 at (site, k) (scpqp_noise_fill)."""
+    if not isinstance(rng, NoiseStream):
+        raise TypeError("rng must be a NoiseStream")
+    device = torch.device(device or "cuda")
+    lib = LB.load()
+    out = torch.empty((int(B), int(n_veh), int(n_eval), 2), dtype=torch.float64, device=device)
+    ns = rng.c_struct()
+    LB.check(lib.scpqp_noise_fill(C.byref(ns), int(B), int(n_veh), int(site), int(k), int(n_eval),
+                                  _ptr(out), _stream(device)), lib)
+    return out
+
+
+def draw_ec_noise(rng, B, n_veh, device=None):
+    """ec_noise [B, n_veh, 2] of ScpQpSolver.solve / linearize / evaluate: the draws of
+    the one ode call inside comp_jacobian (Model.py:58) at ``rng.epoch``."""
+    return noise_fill(rng, B, n_veh, LB.NOISE_SITE_LINEARIZE, 0, 1, device).view(int(B), int(n_veh), 2)
 
 
 def clip_controls(u, u0, umax, n_veh, hp, du_lim):

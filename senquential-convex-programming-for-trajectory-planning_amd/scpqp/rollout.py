@@ -17,7 +17,11 @@ All state lives on the device (torch-ROCm tensors); the per-step index
 bookkeeping (which tick is measured, which control tick each plant output
 reads) is the same for every realisation and is computed on the host once
 per step, exactly as main.py computes it.  Realisations differ by their
-initial state (and optional constant model-noise terms).
+initial state and, with ``reset(..., seed=)``, by the reference's model noise
+(Model.py:84-86): drawn on the device per right-hand-side evaluation from a
+counter-based generator (include/scpqp_noise.h), reproducible from the seed and
+independent of how the realisations are sharded.  ``noise=`` instead holds a
+caller-made constant pair per vehicle over the whole rollout.
 """
 from __future__ import annotations
 
@@ -118,9 +122,21 @@ class ClosedLoopBatch:
         self.out = self.solver.alloc_out(self.B, trace=trace)
         self.history = []
 
-    def reset(self, x_init, noise=None):
+    def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0):
         """main.py:73-75: vehiclePathFullRes[:, v, 0] = x0; the control path holds
-        scenario.u0 for the first ticks_delay_u + ticks_per_sim + 1 ticks."""
+        scenario.u0 for the first ticks_delay_u + ticks_per_sim + 1 ticks.
+
+        ``seed``: run with the reference's model noise (Simulation(..., isNoise);
+        Model.py:84-86), drawn on the device per right-hand-side evaluation: step i uses
+        epoch i for its delay compensation, its plant step and the ec_noise of its solve.
+        Realisation b draws as global realisation ``b_offset + b``, so a batch sharded
+        over ranks (b_offset = rank * per_rank) computes what one large batch would."""
+        if seed is None and getattr(getattr(self.sc, "model", None), "is_noise", False):
+            raise ValueError("scenario.model.is_noise is set: pass reset(..., seed=...) to run "
+                             "the rollout with model noise (it never runs noise-free silently)")
+        if seed is not None and noise is not None:
+            raise ValueError("pass either noise (constant terms) or seed, not both")
+        self.rng = None if seed is None else PL.NoiseStream(seed, sigma, 0, b_offset)
         x = torch.as_tensor(np.asarray(x_init, float) if not isinstance(x_init, torch.Tensor)
                             else x_init, dtype=torch.float64, device=self.device)
         if tuple(x.shape) != (self.B, self.nV, 6):
@@ -177,12 +193,17 @@ class ClosedLoopBatch:
         u_hold = torch.zeros((B, nV), **f) if src is None else self.control[:, :, src].contiguous()
         # IterClass delay compensation (MPC_Iter.py:24-33)
         horizon = sc.delay_x + sc.dt + sc.delay_u
+        # with a seed: this step's noise stream (epoch i), else None and nothing changes
+        rng = None if self.rng is None else self.rng.at(i)
         x0, dtraj = PL.delay_compensate(self.params, x_meas.contiguous(), u_hold, horizon,
-                                        noise=self.noise, h_max=self.h_max, device=self.device)
+                                        noise=self.noise, h_max=self.h_max, device=self.device,
+                                        rng=rng)
         # SCP solve, warm-started from the previous controller output (SCP_controller.py:42-43)
         obst = self._obstacle_prediction(max(0, tick_now - self.tdx))
         u_warm = self.u_prev
-        out = self.solver.solve(x0, u_hold, u_warm=u_warm, obst=obst, out=self.out)
+        # the draws of comp_jacobian's one ode call (Model.py:58)
+        ec_noise = None if rng is None else PL.draw_ec_noise(rng, B, nV, self.device)
+        out = self.solver.solve(x0, u_hold, ec_noise, u_warm=u_warm, obst=obst, out=self.out)
         self.u_prev = out.u.clone()
         if self.timing:
             torch.cuda.synchronize(self.device)
@@ -200,11 +221,14 @@ class ClosedLoopBatch:
         idx = [min(self.ticks_total, math.ceil(t / sc.tick_length) + 1) for t in timelist]
         u_tick = self.control[:, :, torch.as_tensor(idx, device=self.device)].contiguous()
         path = PL.plant_step(self.params, self.state, u_tick, sc.tick_length, noise=self.noise,
-                             h_max=self.h_max, device=self.device)
+                             h_max=self.h_max, device=self.device, rng=rng)
         self.last_path = path
         self.state = path[:, :, tps, :].contiguous()
         rec = dict(x0=x0, u0=u_hold, umax=umax, U=U, traj=out.traj.clone(),
                    n_scp=out.n_scp.clone(), status=out.status.clone())
+        if rng is not None:
+            rec["ec_noise"] = ec_noise
+            rec["epoch"] = i
         if self.evaluate:
             # main.py:201-202: evaluateInOriginalProblem on the clipped U and the prediction
             ref = self.solver.sample_reference(x0)

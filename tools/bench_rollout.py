@@ -7,10 +7,12 @@ CPU: the restatement ``oracle.plant_reference.ClosedLoop`` (the reference's
 scipy calls + the structured SCP restatement) on a bounded sample, one
 realisation per spawned single-threaded worker.
 
-    python tools/bench_rollout.py [B] [steps] [cpu_sample]
+    python tools/bench_rollout.py [B] [steps] [cpu_sample] [--noise-seed S]
 
 Prints one JSON line: realisation-steps/s on the GPU and the CPU, and the
-largest state difference between the two on the CPU sample.
+largest state difference between the two on the CPU sample.  ``--noise-seed S``
+runs the GPU rollout with the reference's model noise (include/scpqp_noise.h);
+the CPU sample stays noise-free, so the state difference then shows the noise.
 """
 import json
 import multiprocessing as mp
@@ -49,9 +51,15 @@ def _cpu_worker(args):
 
 
 def main():
-    B = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-    cpu_n = int(sys.argv[3]) if len(sys.argv) > 3 else 16
+    argv = sys.argv[1:]
+    noise_seed = None
+    if "--noise-seed" in argv:
+        at = argv.index("--noise-seed")
+        noise_seed = int(argv[at + 1], 0)
+        del argv[at:at + 2]
+    B = int(argv[0]) if len(argv) > 0 else 1024
+    steps = int(argv[1]) if len(argv) > 1 else 5
+    cpu_n = int(argv[2]) if len(argv) > 2 else 16
     hp = 20
     from oracle import scp_reference as R
     sc = R.circle_scenario(4, Hp=hp)
@@ -65,10 +73,10 @@ def main():
     import torch
     from scpqp.rollout import ClosedLoopBatch
     cl = ClosedLoopBatch(sc, B, device="cuda")
-    cl.reset(x_init)
+    cl.reset(x_init, seed=noise_seed)
     cl.run(1)                      # warm-up (library load, first launches)
     torch.cuda.synchronize()
-    cl.reset(x_init)
+    cl.reset(x_init, seed=noise_seed)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     hist = cl.run(steps)
@@ -80,7 +88,7 @@ def main():
     print(json.dumps({
         "metric": "closed-loop MPC realisation-steps/s (4 veh, Hp=20)",
         "gpu_value": B * steps / gpu_s, "gpu_ms_per_step": gpu_s / steps * 1e3, "batch": B,
-        "steps": steps,
+        "steps": steps, "noise_seed": noise_seed,
         "cpu_value": cpu_n * steps / cpu_wall, "cpu_workers": cpu_n,
         "cpu_sample": f"{cpu_n} realisations x {steps} steps, oracle ClosedLoop (scipy odeint/dopri5 "
                       f"+ structured SCP restatement), one spawned single-threaded worker each",

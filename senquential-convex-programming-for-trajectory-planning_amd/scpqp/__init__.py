@@ -3,6 +3,7 @@
 Public API:
   ScpQpSolver   batched solver bound to one scenario (C-ABI in include/scpqp.h)
   batch         synthetic problem batches
+  PathMetrics   realised-path metrics of closed-loop rollouts (include/scpqp_metrics.h)
   build_library compile csrc/scpqp.hip for gfx950 into scpqp/libscpqp.so
 """
 from .build import build_library, LIB_PATH  # noqa: F401
@@ -14,4 +15,7 @@ def __getattr__(name):
     if name in ("ScpQpSolver", "SolveResult", "unpack_problem"):
         from . import solver
         return getattr(solver, name)
+    if name == "PathMetrics":
+        from . import metrics
+        return metrics.PathMetrics
     raise AttributeError(name)

@@ -1,5 +1,5 @@
-"""ctypes binding of ``include/scpqp.h`` and ``include/scpqp_noise.h`` (the C-ABI of the
-HIP library).
+"""ctypes binding of ``include/scpqp.h``, ``include/scpqp_noise.h`` and
+``include/scpqp_metrics.h`` (the C-ABI of the HIP library).
 
 The shared library ``libscpqp.so`` is built in-tree (``__graft_entry__.build()``
 or ``python -m scpqp.build``).  There is no CPU fallback: if the library or a
@@ -96,6 +96,34 @@ NOISE_SITE_DELAY, NOISE_SITE_PLANT, NOISE_SITE_LINEARIZE = 0, 1, 2
 # every symbol include/scpqp_noise.h declares (checked by tests/test_noise_host.py)
 NOISE_EXPORTS = ("scpqp_delay_compensate_noisy", "scpqp_plant_step_noisy", "scpqp_noise_fill")
 
+
+
+class MetricsParams(C.Structure):
+    """scpqp_metrics_params (include/scpqp_metrics.h): host pointers, copied at create."""
+    _fields_ = [("n_veh", C.c_int32), ("n_obst", C.c_int32), ("ref_max_pts", C.c_int32),
+                ("pad0", C.c_int32), ("tick_length", C.c_double), ("length", _dp), ("width", _dp),
+                ("dsafe_veh", _dp), ("dsafe_obs", _dp), ("obstacles", _dp), ("ref_polyline", _dp),
+                ("ref_npts", _ip)]
+
+
+# the accumulator arrays of scpqp_metrics_acc, in the order of the structure
+METRICS_ACC_FIELDS = ("min_gap_veh", "min_gap_obs", "min_margin_veh", "min_margin_obs",
+                      "argmin_gap_veh", "argmin_gap_obs", "first_collision_tick",
+                      "n_collision_ticks", "n_ticks_seen", "max_xtrack", "sum_sq_xtrack")
+
+
+class MetricsAcc(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in METRICS_ACC_FIELDS]
+
+
+class MetricsDense(C.Structure):
+    _fields_ = [("gap_veh", C.c_void_p), ("gap_obs", C.c_void_p), ("xtrack", C.c_void_p)]
+
+
+# every symbol include/scpqp_metrics.h declares (checked by tests/test_metrics_host.py)
+METRICS_EXPORTS = ("scpqp_metrics_create", "scpqp_metrics_destroy", "scpqp_metrics_reset",
+                   "scpqp_metrics_accumulate")
+
 _lib = None
 
 
@@ -152,6 +180,16 @@ def load(path=None):
     lib.scpqp_plant_step_noisy.restype = C.c_int
     lib.scpqp_noise_fill.argtypes = [NP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, V, V]
     lib.scpqp_noise_fill.restype = C.c_int
+    MA, MD = C.POINTER(MetricsAcc), C.POINTER(MetricsDense)
+    lib.scpqp_metrics_create.argtypes = [C.POINTER(MetricsParams), C.c_int, C.POINTER(H)]
+    lib.scpqp_metrics_create.restype = C.c_int
+    lib.scpqp_metrics_destroy.argtypes = [H]
+    lib.scpqp_metrics_destroy.restype = C.c_int
+    lib.scpqp_metrics_reset.argtypes = [H, C.c_int32, MA, V]
+    lib.scpqp_metrics_reset.restype = C.c_int
+    lib.scpqp_metrics_accumulate.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, V, MA,
+                                             MD, V]
+    lib.scpqp_metrics_accumulate.restype = C.c_int
     if path is None:
         _lib = lib
     return lib

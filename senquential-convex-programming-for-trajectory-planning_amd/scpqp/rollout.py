@@ -12,6 +12,9 @@ for B independent realisations of one scenario at once.  Per MPC step i:
                                                             -> scpqp_plant_step
 6. evaluateInOriginalProblem of the step (main.py:201-202, SCP_controller.py:343-400)
                                                             -> device tensor ops
+7. with ``metrics=True``: footprint gaps, collisions, margins to dsafe and cross-track
+   errors along the step's realised path, merged into a per-realisation accumulator
+   (scpqp/metrics.py)                                       -> scpqp_metrics_accumulate
 
 All state lives on the device (torch-ROCm tensors); the per-step index
 bookkeeping (which tick is measured, which control tick each plant output
@@ -92,7 +95,7 @@ def held_command_tick(tick_now, tdx, tdu, tps, ticks_total):
 
 class ClosedLoopBatch:
     def __init__(self, scenario, B, device=None, h_max=PL.H_MAX, keep_path=False, evaluate=True,
-                 timing=False, trace=False, **solver_kw):
+                 timing=False, trace=False, metrics=False, **solver_kw):
         self.sc = scenario
         self.B = int(B)
         self.device = torch.device(device or "cuda")
@@ -121,6 +124,11 @@ class ClosedLoopBatch:
         self.trace = trace      # keep every step's solve inputs and per-SCP-iteration trace
         self.out = self.solver.alloc_out(self.B, trace=trace)
         self.history = []
+        # realised-path metrics (scpqp/metrics.py); off: nothing is allocated or launched
+        self.path_metrics = None
+        if metrics:
+            from .metrics import PathMetrics
+            self.path_metrics = PathMetrics(scenario, self.B, self.device)
 
     def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0):
         """main.py:73-75: vehiclePathFullRes[:, v, 0] = x0; the control path holds
@@ -152,6 +160,8 @@ class ClosedLoopBatch:
         self.u_prev = None
         self.history = []
         self.i = 0
+        if self.path_metrics is not None:
+            self.path_metrics.reset(self.B)
 
     def _obstacle_prediction(self, tick_meas):
         """Iter.obstacleFutureTrajectories (MPC_Iter.py:45-51) from the constant-velocity
@@ -222,6 +232,9 @@ class ClosedLoopBatch:
         u_tick = self.control[:, :, torch.as_tensor(idx, device=self.device)].contiguous()
         path = PL.plant_step(self.params, self.state, u_tick, sc.tick_length, noise=self.noise,
                              h_max=self.h_max, device=self.device, rng=rng)
+        if self.path_metrics is not None:
+            # every global tick once: entry 0 of a later step is the previous step's last
+            self.path_metrics.accumulate(path, tick0=i * tps, k_first=0 if i == 0 else 1)
         self.last_path = path
         self.state = path[:, :, tps, :].contiguous()
         rec = dict(x0=x0, u0=u_hold, umax=umax, U=U, traj=out.traj.clone(),
@@ -312,5 +325,20 @@ class ClosedLoopBatch:
         res = self.result_for_plot(b)
         json.dump({k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in res.items()}, fp)
 
+    def metrics(self):
+        """The realised-path metrics of the steps run since reset(): a dict of device
+        tensors per realisation (``PathMetrics.result``; needs ``metrics=True``)."""
+        if self.path_metrics is None:
+            raise ValueError("metrics() needs ClosedLoopBatch(..., metrics=True)")
+        return self.path_metrics.result()
+
+    def metrics_summary(self):
+        """``metrics.summarize`` of this batch: collision rate, clearance quantiles and
+        cross-track figures as plain Python numbers."""
+        from .metrics import summarize
+        return summarize(self.metrics())
+
     def close(self):
+        if self.path_metrics is not None:
+            self.path_metrics.close()
         self.solver.close()

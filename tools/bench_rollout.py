@@ -7,12 +7,14 @@ CPU: the restatement ``oracle.plant_reference.ClosedLoop`` (the reference's
 scipy calls + the structured SCP restatement) on a bounded sample, one
 realisation per spawned single-threaded worker.
 
-    python tools/bench_rollout.py [B] [steps] [cpu_sample] [--noise-seed S]
+    python tools/bench_rollout.py [B] [steps] [cpu_sample] [--noise-seed S] [--metrics]
 
 Prints one JSON line: realisation-steps/s on the GPU and the CPU, and the
 largest state difference between the two on the CPU sample.  ``--noise-seed S``
 runs the GPU rollout with the reference's model noise (include/scpqp_noise.h);
 the CPU sample stays noise-free, so the state difference then shows the noise.
+``--metrics`` accumulates the realised-path metrics (scpqp/metrics.py) during the timed
+run and adds their batch summary: collision rate, clearance quantiles, cross-track error.
 """
 import json
 import multiprocessing as mp
@@ -57,6 +59,9 @@ def main():
         at = argv.index("--noise-seed")
         noise_seed = int(argv[at + 1], 0)
         del argv[at:at + 2]
+    metrics = "--metrics" in argv
+    if metrics:
+        argv.remove("--metrics")
     B = int(argv[0]) if len(argv) > 0 else 1024
     steps = int(argv[1]) if len(argv) > 1 else 5
     cpu_n = int(argv[2]) if len(argv) > 2 else 16
@@ -72,7 +77,7 @@ def main():
 
     import torch
     from scpqp.rollout import ClosedLoopBatch
-    cl = ClosedLoopBatch(sc, B, device="cuda")
+    cl = ClosedLoopBatch(sc, B, device="cuda", metrics=metrics)
     cl.reset(x_init, seed=noise_seed)
     cl.run(1)                      # warm-up (library load, first launches)
     torch.cuda.synchronize()
@@ -85,7 +90,8 @@ def main():
     state = cl.state.cpu().numpy()
     diff = max(float(np.abs(state[b] - cpu[b][1]).max()) for b in range(cpu_n))
     feas = float(np.mean([h["evaluation"]["predictionFeasible"].float().mean().item() for h in hist]))
-    print(json.dumps({
+    summary = cl.metrics_summary() if metrics else None
+    out = {
         "metric": "closed-loop MPC realisation-steps/s (4 veh, Hp=20)",
         "gpu_value": B * steps / gpu_s, "gpu_ms_per_step": gpu_s / steps * 1e3, "batch": B,
         "steps": steps, "noise_seed": noise_seed,
@@ -95,7 +101,10 @@ def main():
         "max_state_diff_vs_cpu": diff,
         "predicted_feasible_frac": feas,
         "mean_scp_iters": float(np.mean([h["n_scp"].float().mean().item() for h in hist])),
-    }))
+    }
+    if metrics:
+        out["metrics"] = summary
+    print(json.dumps(out))
     cl.close()
 
 

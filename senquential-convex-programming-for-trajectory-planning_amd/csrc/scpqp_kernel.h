@@ -151,7 +151,7 @@ typedef __attribute__((address_space(4))) const DevParams cParams;
 // ---------------------------------------------------------------------------
 // Memory plan: integer offsets (doubles).  Persistent LDS arrays first, then a
 // union region used by the setup scratch (expm) and, during the solve, by the
-// KKT matrix, the W~ blocks and the 9 constraint-space vectors (those marked
+// KKT matrix, the W~ blocks and the 7 constraint-space vectors (those marked
 // global go to the per-workgroup workspace instead).  Sizes use hp_max;
 // indexing uses the problem's own horizon, so mixed horizons share a launch.
 // ---------------------------------------------------------------------------
@@ -183,6 +183,18 @@ __host__ __device__ constexpr int red_size(bool hG) { return kPivSlot + 2 * (hG 
 // the lean plan 1 (W~ blocks and constraint rows in the workspace beside the vectors) at
 // two workgroups per CU (c5, Hp 30), or four (the round-6 c2 residency experiment)
 __host__ __device__ constexpr bool lean_plan(bool hG, bool vG, int occ) { return !hG && vG && (occ == 2 || occ == 4); }
+// plan 1 at three workgroups per CU keeps tv, the one constraint-space vector that other
+// threads read three times per IPM iteration (gt_apply_fin), in LDS, in the storage of pb:
+// pb (the positions of the last evaluated u) is live from an evaluation to the next
+// linearisation or the outputs, tv only inside a QP solve, which lies between a
+// linearisation and the next evaluation and writes tv before it reads it (ph_init_a,
+// polish_rhs_body).  (= Lay::TVLDS)
+__host__ __device__ constexpr bool tv_in_lds(bool hG, bool vG, bool lean) { return !hG && vG && !lean; }
+
+// The constraint-space vectors of a plan: s lam rp dd sa la tv.  The Newton direction
+// (ds, dl) has no storage of its own: it lives in sa / la, where the affine step keeps it
+// for the corrector anyway (Rows, below).
+constexpr int kVecs = 7;
 
 struct Off {
     int x0, u0, ec, g, p0, ref, ob, ub, pb, ya, yb, qs, rowE, rowW, rowH, rinfo;
@@ -212,7 +224,8 @@ __host__ __device__ inline Off plan_offsets(int V, int O, int Hm, bool hG, bool 
     f.ref = p; p += pad2(2 * N);
     f.ob = p; p += pad2(2 * O * Hm);
     f.ub = p; p += pad2(N);
-    f.pb = p; p += pad2(2 * N);
+    const bool tvL = tv_in_lds(hG, vG, lean);
+    f.pb = p; p += tvL ? pad2(mc) : pad2(2 * N);   // mc > 2 N
     f.ya = p; p += pad2(2 * N);
     f.yb = p; p += pad2(2 * N);
     f.qs = p; p += pad2(N);
@@ -241,7 +254,8 @@ __host__ __device__ inline Off plan_offsets(int V, int O, int Hm, bool hG, bool 
     const bool wG = (hG && vG && (n + 63) / 64 == 4) || lean;   // = Lay::WGLOBAL
     const bool rows_scr = wG && !lean && f.rinfo + pad2((m + 1) / 2) - f.rowE >= setup;
     if (wG) { f.Wt = w; w += pad2(4 * Hm * nb); } else { f.Wt = p + u; u += pad2(4 * Hm * nb); }
-    if (vG) { f.vec = w; w += 9 * pad2(mc); } else { f.vec = p + u; u += 9 * pad2(mc); }
+    const int nvec = tvL ? kVecs - 1 : kVecs;   // tv last: in pb's storage when tvL
+    if (vG) { f.vec = w; w += nvec * pad2(mc); } else { f.vec = p + u; u += nvec * pad2(mc); }
     f.uni = u > setup ? u : setup;
     if (rows_scr) {
         f.scr = f.rowE;
@@ -275,7 +289,11 @@ struct Lay {
     RIT* rinfo;
     WT* Wt;
     HT* H;
-    VT *s, *lam, *ds, *dl, *rp, *dd, *sa, *la, *tv;
+    VT *s, *lam, *rp, *dd, *sa, *la;
+    // tv: in LDS (pb's storage) on plan 1 at three workgroups per CU (tv_in_lds)
+    static constexpr bool TVLDS = tv_in_lds(HG, VG, LEAN);
+    using TT = typename std::conditional<TVLDS, ldouble, VT>::type;
+    TT* tv;
 };
 
 // Problem shapes compiled as constants (template SH): the vehicle count, obstacle
@@ -339,8 +357,9 @@ __device__ __forceinline__ Lay<HG, VG, RM, OCC> make_lay(ldouble* lds, gdouble* 
     typename Lay<HG, VG, RM, OCC>::VT* vb;
     if constexpr (VG) vb = ws + f.vec; else vb = lds + f.vec;
     const int st = f.mcAlloc;
-    L.s = vb; L.lam = vb + st; L.ds = vb + 2 * st; L.dl = vb + 3 * st; L.rp = vb + 4 * st;
-    L.dd = vb + 5 * st; L.sa = vb + 6 * st; L.la = vb + 7 * st; L.tv = vb + 8 * st;
+    L.s = vb; L.lam = vb + st; L.rp = vb + 2 * st; L.dd = vb + 3 * st;
+    L.sa = vb + 4 * st; L.la = vb + 5 * st;
+    if constexpr (Lay<HG, VG, RM, OCC>::TVLDS) L.tv = lds + f.pb; else L.tv = vb + 6 * st;
     return L;
 }
 
@@ -2000,19 +2019,128 @@ __device__ void g_apply(const LT& L, PX x, PO out, bool minus_h) {
     bar();
 }
 
-// residuals rd (n), rp (mc) at (z, s, lam); out = {max|rp|, max|rd|, gap, pobj}
+// ---------------------------------------------------------------------------
+// Row values.  Row r of the constraint-space vectors s lam rp dd sa la is only ever
+// touched by thread r mod NT, in slot r / NT of that thread's rows.  The step bodies
+// below reach these six through an accessor, of which there are two:
+//   RowsMem  every access goes to the vector's storage (workspace or LDS), as before;
+//   RowsReg  the thread keeps its rows' values in registers through an out-of-line
+//            phase: load<fields>() at the top of the phase, where the loads overlap the
+//            Toeplitz product that every phase starts with, and store<fields>() once,
+//            for the fields a later phase or another thread reads.  Between the bodies of
+//            a phase nothing goes through memory, so a body does not start with a
+//            dependent round trip to L2 for values the same thread formed in the body
+//            before it.
+// RowsReg serves the kernels whose slot count is a compile-time constant of at most
+// kCarrySlots (shape 1 and c5's classes: 6 doubles of state per slot); the others (c3:
+// 6 slots; the run-time shape) take RowsMem.  The Newton direction (ds, dl) is stored in
+// (sa, la) in both: the predictor's direction is what the affine step keeps there, and
+// the corrector reads a row's sa la (for rc) before it forms that row's ds dl.
+// tv is not a row value in this sense: other threads read it (gt_apply_fin).
+// ---------------------------------------------------------------------------
+enum : int { RV_S = 1, RV_LAM = 2, RV_RP = 4, RV_DD = 8, RV_SA = 16, RV_LA = 32 };
+constexpr int kCarrySlots = 2;
+// row slots of a shape's QPs; 0 when the horizon is not compiled in
+template <int SH>
+__host__ __device__ constexpr int row_slots() {
+    const ShapeC c = shape_c(SH);
+    if (!c.H) return 0;
+    const int N = c.V * c.H, m = c.V * (c.V - 1) / 2 * c.H + c.V * c.O * c.H;
+    return (m + 2 * N + 1 + NT - 1) / NT;
+}
+
 template <class LT>
-__device__ void residuals(const cParams& P, const LT& L, double (&out)[4]) {
+struct RowsMem {
+    static constexpr int NS = 0;
+    using Ref = typename LT::VT&;
+    const LT& L;
+    __device__ __forceinline__ Ref s(int, int r) const { return L.s[r]; }
+    __device__ __forceinline__ Ref lam(int, int r) const { return L.lam[r]; }
+    __device__ __forceinline__ Ref rp(int, int r) const { return L.rp[r]; }
+    __device__ __forceinline__ Ref dd(int, int r) const { return L.dd[r]; }
+    __device__ __forceinline__ Ref sa(int, int r) const { return L.sa[r]; }
+    __device__ __forceinline__ Ref la(int, int r) const { return L.la[r]; }
+    __device__ __forceinline__ Ref ds(int, int r) const { return L.sa[r]; }
+    __device__ __forceinline__ Ref dl(int, int r) const { return L.la[r]; }
+    template <int F>
+    __device__ __forceinline__ void load() {}
+    template <int F>
+    __device__ __forceinline__ void store() const {}
+};
+template <class LT, int NSLOT>
+struct RowsReg {
+    static constexpr int NS = NSLOT;
+    const LT& L;
+    double s_[NSLOT], lam_[NSLOT], rp_[NSLOT], dd_[NSLOT], sa_[NSLOT], la_[NSLOT];
+    __device__ __forceinline__ double& s(int k, int) { return s_[k]; }
+    __device__ __forceinline__ double& lam(int k, int) { return lam_[k]; }
+    __device__ __forceinline__ double& rp(int k, int) { return rp_[k]; }
+    __device__ __forceinline__ double& dd(int k, int) { return dd_[k]; }
+    __device__ __forceinline__ double& sa(int k, int) { return sa_[k]; }
+    __device__ __forceinline__ double& la(int k, int) { return la_[k]; }
+    __device__ __forceinline__ double& ds(int k, int) { return sa_[k]; }
+    __device__ __forceinline__ double& dl(int k, int) { return la_[k]; }
+    template <int F>
+    __device__ __forceinline__ void load() {
+#pragma unroll
+        for (int k = 0; k < NSLOT; ++k) {
+            const int r = threadIdx.x + k * NT;
+            if (r >= L.mc) continue;
+            if (F & RV_S) s_[k] = L.s[r];
+            if (F & RV_LAM) lam_[k] = L.lam[r];
+            if (F & RV_RP) rp_[k] = L.rp[r];
+            if (F & RV_DD) dd_[k] = L.dd[r];
+            if (F & RV_SA) sa_[k] = L.sa[r];
+            if (F & RV_LA) la_[k] = L.la[r];
+        }
+    }
+    template <int F>
+    __device__ __forceinline__ void store() const {
+#pragma unroll
+        for (int k = 0; k < NSLOT; ++k) {
+            const int r = threadIdx.x + k * NT;
+            if (r >= L.mc) continue;
+            if (F & RV_S) L.s[r] = s_[k];
+            if (F & RV_LAM) L.lam[r] = lam_[k];
+            if (F & RV_RP) L.rp[r] = rp_[k];
+            if (F & RV_DD) L.dd[r] = dd_[k];
+            if (F & RV_SA) L.sa[r] = sa_[k];
+            if (F & RV_LA) L.la[r] = la_[k];
+        }
+    }
+};
+template <int SH, class LT>
+using RowsOf = typename std::conditional<(row_slots<SH>() >= 1 && row_slots<SH>() <= kCarrySlots),
+                                         RowsReg<LT, (row_slots<SH>() >= 1 ? row_slots<SH>() : 1)>,
+                                         RowsMem<LT>>::type;
+// fn(slot, r) for this thread's rows r = tid + slot NT < mc, in increasing r
+template <class RW, class Fn>
+__device__ __forceinline__ void each_row(const RW&, int mc, Fn fn) {
+    if constexpr (RW::NS > 0) {
+#pragma unroll
+        for (int k = 0; k < RW::NS; ++k) {
+            const int r = threadIdx.x + k * NT;
+            if (r < mc) fn(k, r);
+        }
+    } else {
+        for (int r = threadIdx.x; r < mc; r += NT) fn(0, r);
+    }
+}
+
+// residuals rd (n), rp (mc) at (z, s, lam); out = {max|rp|, max|rd|, gap, pobj}.
+// A holds s and lam; lam is also in its storage (other threads' rows are read below).
+template <class LT, class RW>
+__device__ void residuals(const cParams& P, const LT& L, RW& A, double (&out)[4]) {
     const int tid = threadIdx.x, N = L.N, Hb = L.Hb;
     const double u2 = P.uLim * P.uLim;
     toeplitz_apply(L, L.z, L.ya);
     bar();
     const double zw = L.z[N];
     double mrp = 0.0, gap = 0.0, wl = 0.0, quad = 0.0;
-    for (int r = tid; r < L.mc; r += NT) {
-        const double sr = L.s[r], lr = L.lam[r];
+    each_row(A, L.mc, [&](int k, int r) {
+        const double sr = A.s(k, r), lr = A.lam(k, r);
         const double v = gx_row(L, L.z, zw, r) + sr - hval(L, r);
-        L.rp[r] = v;
+        A.rp(k, r) = v;
         mrp = fmax(mrp, fabs(v));
         gap += sr * lr;
         if (r < L.m) wl += lr * L.rowW[r];
@@ -2020,9 +2148,10 @@ __device__ void residuals(const cParams& P, const LT& L, double (&out)[4]) {
         // tv = d rp - (s lam) / s (round 5: formed here, in the thread that owns row r,
         // instead of two passes and two barriers of the factorisation phase)
         const double is = recip(sr), dr = lr * is;
-        L.dd[r] = dr;
+        A.dd(k, r) = dr;
         L.tv[r] = dr * v - (sr * lr) * is;
-    }
+    });
+    A.template store<RV_RP | RV_DD>();   // rp: the next phase's row owner; dd: assemble
     for (int e = tid; e < L.V * Hb; e += NT) {
         const int v = e / Hb, k = e % Hb;
         const double qk = 2.0 * u2 * ((k == Hb - 1) ? P.Qf[v] : P.Q[v]);
@@ -2113,6 +2242,8 @@ __device__ __forceinline__ Lay<HG, VG, RM, OCC> lay_of(const Ctx& c) {
     const Lay<HG, VG, RM, OCC> L = lay_of<HG, VG, RM, OCC, SH>(cu_); \
     (void)P
 #define PH(f) f<HG, VG, RM, OCC, SH>
+// this thread's row values of the phase (RowsReg where the shape carries them, else RowsMem)
+#define ROWSDEF RowsOf<SH, Lay<HG, VG, RM, OCC>> A{L}
 
 // x = K^{-1} rhs into z (dst = 0) or dz (dst = 1)
 PHASE void ph_solve(Ctx c, int dst) {
@@ -2129,8 +2260,10 @@ PHASE EvalRes ph_evaluate(Ctx c, double* cveh, double* cobs) {
 }
 PHASE D4 ph_residuals(Ctx c) {
     LAYDEF;
+    ROWSDEF;
+    A.template load<RV_S | RV_LAM>();
     double r[4];
-    residuals(P, L, r);
+    residuals(P, L, A, r);
     return D4{r[0], r[1], r[2], r[3]};
 }
 // rhs = -q + G'(tv) with tv = h (init) or tv = mask (h/delta - y) (polish), + rho x_k.
@@ -2213,13 +2346,13 @@ PHASE void ph_init_b(Ctx c) {
 //
 // Newton direction, complementarity target rc = s lam (+ ds_aff dl_aff - smu if corr):
 //   rhs = -rd - G'(d rp - rc/s);  dz = K^{-1} rhs;  ds = -rp - G dz;  dl = -(rc + lam ds)/s
-template <bool TV = true, class LT>
-__device__ __forceinline__ void newton_rhs_body(const LT& L, int corr, double smu) {
+template <bool TV = true, class LT, class RW>
+__device__ __forceinline__ void newton_rhs_body(const LT& L, RW& A, int corr, double smu) {
     if constexpr (TV) {   // else tv is already formed (the predictor: residuals())
-        for (int r = threadIdx.x; r < L.mc; r += NT) {
-            const double rc = L.s[r] * L.lam[r] + (corr ? L.sa[r] * L.la[r] - smu : 0.0);
-            L.tv[r] = L.dd[r] * L.rp[r] - rc * recip(L.s[r]);
-        }
+        each_row(A, L.mc, [&](int k, int r) {
+            const double rc = A.s(k, r) * A.lam(k, r) + (corr ? A.sa(k, r) * A.la(k, r) - smu : 0.0);
+            L.tv[r] = A.dd(k, r) * A.rp(k, r) - rc * recip(A.s(k, r));
+        });
         bar();
     }
     // buffer 0: reached after assemble's closing barrier or the tv pass's barrier
@@ -2231,36 +2364,40 @@ __device__ __forceinline__ void newton_rhs_body(const LT& L, int corr, double sm
 // partial step lengths {primal: min over ds < 0 of -s/ds, dual: min over dl < 0 of
 // -lam/dl} from the values it just formed (round 5: one barrier and one pass over the
 // rows fewer than G dz, the direction and the ratio tests apart; the same operations).
-template <class LT>
-__device__ __forceinline__ double2v newton_back_body(const LT& L, int corr, double smu) {
+// The direction goes to (sa, la) (Rows): with corr, the row's affine direction there has
+// just been used for rc.  A holds s lam rp (and sa la with corr).
+template <class LT, class RW>
+__device__ __forceinline__ double2v newton_back_body(const LT& L, RW& A, int corr, double smu) {
     toeplitz_apply(L, L.dz, L.ya);
     bar();
     const double xw = L.dz[L.N];
     double ap = 1.0, ad = 1.0;
-    for (int r = threadIdx.x; r < L.mc; r += NT) {
-        const double rc = L.s[r] * L.lam[r] + (corr ? L.sa[r] * L.la[r] - smu : 0.0);
-        const double dsr = -L.rp[r] - gx_row(L, L.dz, xw, r);
-        const double dlr = -(rc + L.lam[r] * dsr) * recip(L.s[r]);
-        L.ds[r] = dsr;
-        L.dl[r] = dlr;
-        if (dsr < 0.0) ap = fmin(ap, -L.s[r] * recip(dsr));
-        if (dlr < 0.0) ad = fmin(ad, -L.lam[r] * recip(dlr));
-    }
-    bar();
+    each_row(A, L.mc, [&](int k, int r) {
+        const double rc = A.s(k, r) * A.lam(k, r) + (corr ? A.sa(k, r) * A.la(k, r) - smu : 0.0);
+        const double dsr = -A.rp(k, r) - gx_row(L, L.dz, xw, r);
+        const double dlr = -(rc + A.lam(k, r) * dsr) * recip(A.s(k, r));
+        A.ds(k, r) = dsr;
+        A.dl(k, r) = dlr;
+        if (dsr < 0.0) ap = fmin(ap, -A.s(k, r) * recip(dsr));
+        if (dlr < 0.0) ad = fmin(ad, -A.lam(k, r) * recip(dlr));
+    });
+    // No barrier here (there was one until the direction left the memory plan): the rows
+    // above are read and written by their own thread only, ya is not written again before
+    // the barrier of the reduction that follows in either caller, and that reduction's
+    // buffer 0 was last read before the closing barrier of the phase before the solve.
     return double2v{ap, ad};
 }
 // predictor step length and Mehrotra centring: returns sigma * mu; stores the affine direction
-template <class LT>
-__device__ __forceinline__ double affine_body(const LT& L, double mu, double2v part) {
+// (the affine direction is where newton_back_body left it: sa, la)
+template <class LT, class RW>
+__device__ __forceinline__ double affine_body(const LT& L, RW& A, double mu, double2v part) {
     double redm[4] = {-fmin(part.x, part.y), 0.0, 0.0, 0.0};
     block_reduce4<1>(redm, 1, L.red);   // = max_step(L)
     const double aaff = -redm[0];
     double mua = 0.0;
-    for (int r = threadIdx.x; r < L.mc; r += NT) {
-        mua += (L.s[r] + aaff * L.ds[r]) * (L.lam[r] + aaff * L.dl[r]);
-        L.sa[r] = L.ds[r];
-        L.la[r] = L.dl[r];
-    }
+    each_row(A, L.mc, [&](int k, int r) {
+        mua += (A.s(k, r) + aaff * A.ds(k, r)) * (A.lam(k, r) + aaff * A.dl(k, r));
+    });
     double red[4] = {mua, 0.0, 0.0, 0.0};
     block_reduce4<1, 1>(red, 0, L.red);   // follows max_step's (buffer 0)
     const double sr = red[0] / L.mc / mu;
@@ -2272,8 +2409,8 @@ __device__ __forceinline__ double affine_body(const LT& L, double mu, double2v p
 // iteration's residuals absorb.  CPU study, cold IPM iterations per QP: c2 11.4 -> 10.9,
 // Hp 30 11.0 -> 10.1, c3 14.0 -> 13.1 (max 23 -> 19), frog 15.9 -> 11.0; Hp 10 and
 // parallel5 unchanged; every polish certifies the same minimiser.
-template <class LT>
-__device__ __forceinline__ void update_body(const LT& L, double eta, double2v part) {
+template <class LT, class RW>
+__device__ __forceinline__ void update_body(const LT& L, RW& A, double eta, double2v part) {
     // separate step lengths: (z, s) by the primal ratio test, lam by the dual one
     double ap = part.x, ad = part.y;
     double red[4] = {-ap, -ad, 0.0, 0.0};
@@ -2281,10 +2418,11 @@ __device__ __forceinline__ void update_body(const LT& L, double eta, double2v pa
     ap = fmin(1.0, eta * -red[0]);
     ad = fmin(1.0, eta * -red[1]);
     for (int e = threadIdx.x; e < L.n; e += NT) L.z[e] += ap * L.dz[e];
-    for (int r = threadIdx.x; r < L.mc; r += NT) {
-        L.s[r] += ap * L.ds[r];
-        L.lam[r] += ad * L.dl[r];
-    }
+    each_row(A, L.mc, [&](int k, int r) {
+        A.s(k, r) += ap * A.ds(k, r);
+        A.lam(k, r) += ad * A.dl(k, r);
+    });
+    A.template store<RV_S | RV_LAM>();   // lam: read across threads by residuals()
     bar();
 }
 // Fraction of the step to the boundary (round 3): max(0.99, 1 - mu) instead of a fixed
@@ -2303,7 +2441,8 @@ PHASE int ph_scale_assemble_rhs_factor(Ctx c) {
     PROF_T0_FINE();
     assemble(P, L, L.dd, 0.0);
     PROF_ACC_FINE0(29);
-    newton_rhs_body<false>(L, 0, 0.0);
+    RowsMem<Lay<HG, VG, RM, OCC>> A{L};   // unused: the predictor's tv is already formed
+    newton_rhs_body<false>(L, A, 0, 0.0);
     PROF_ACC_FINE0(28);
     return cholesky(L) ? 1 : 0;
 }
@@ -2326,19 +2465,24 @@ PHASE void ph_init_assemble_factor(Ctx c) {
 // predictor back-substitution, affine step and centring, corrector right-hand side
 PHASE double ph_back_affine_rhs(Ctx c, double mu) {
     LAYDEF;
-    const double2v part = newton_back_body(L, 0, 0.0);
-    const double smu = affine_body(L, mu, part);
-    newton_rhs_body(L, 1, smu);
+    ROWSDEF;
+    A.template load<RV_S | RV_LAM | RV_RP | RV_DD>();
+    const double2v part = newton_back_body(L, A, 0, 0.0);
+    const double smu = affine_body(L, A, mu, part);
+    A.template store<RV_SA | RV_LA>();   // the corrector's rc (ph_back_update_residuals)
+    newton_rhs_body(L, A, 1, smu);
     return smu;
 }
 // corrector back-substitution, the damped step, and the residuals of the new
 // point (the next iteration's convergence test)
 PHASE D4 ph_back_update_residuals(Ctx c, double smu, double eta) {
     LAYDEF;
-    const double2v part = newton_back_body(L, 1, smu);
-    update_body(L, eta, part);
+    ROWSDEF;
+    A.template load<RV_S | RV_LAM | RV_RP | RV_SA | RV_LA>();
+    const double2v part = newton_back_body(L, A, 1, smu);
+    update_body(L, A, eta, part);
     double r[4];
-    residuals(P, L, r);
+    residuals(P, L, A, r);
     return D4{r[0], r[1], r[2], r[3]};
 }
 // polish: weights 1/delta on the active set {lam > s}, y = lam there, x_0 = z
@@ -2378,22 +2522,25 @@ PHASE D4 ph_scales(Ctx c) {
     return D4{red[0], red[1], 0.0, 0.0};
 }
 // polish right-hand side: tv = mask (h / delta - y), rhs = -q + G' tv + rho x_k
-template <class LT>
-__device__ __forceinline__ void polish_rhs_body(const cParams& P, const LT& L) {
+template <class LT, class RW>
+__device__ __forceinline__ void polish_rhs_body(const cParams& P, const LT& L, RW& A) {
     const double idl = L.red[kIdlSlot];
-    for (int r = threadIdx.x; r < L.mc; r += NT) L.tv[r] = L.sa[r] * (hval(L, r) * idl - L.la[r]);
+    each_row(A, L.mc, [&](int k, int r) { L.tv[r] = A.sa(k, r) * (hval(L, r) * idl - A.la(k, r)); });
     bar();
     rhs_from_tv_body(P, L, P.polRho);
 }
 PHASE void ph_polish_rhs(Ctx c) {
     LAYDEF;
-    polish_rhs_body(P, L);
+    ROWSDEF;
+    A.template load<RV_SA | RV_LA>();
+    polish_rhs_body(P, L, A);
 }
 // rp = G x_k - h;  y += rp / delta on the active set.  Returns
 // {max |x_k - x_{k-1}|, max |x_k|, max rp over the inactive rows, -min y over
 // the active rows} (x_{k-1} kept in rd, dead during the polish).
-template <class LT>
-__device__ __forceinline__ D4 polish_dual_body(const cParams& P, const LT& L) {
+// A holds sa (the mask) and la (y).
+template <class LT, class RW>
+__device__ __forceinline__ D4 polish_dual_body(const cParams& P, const LT& L, RW& A) {
     const double idl = L.red[kIdlSlot];
     // rp = G x_k - h row by row in the thread that uses it (round 5: one barrier fewer
     // per multiplier iteration than G x_k - h and the update apart)
@@ -2401,15 +2548,15 @@ __device__ __forceinline__ D4 polish_dual_body(const cParams& P, const LT& L) {
     bar();
     const double xw = L.dz[L.N];
     double viol = -1e300, yneg = -1e300;
-    for (int r = threadIdx.x; r < L.mc; r += NT) {
+    each_row(A, L.mc, [&](int k, int r) {
         const double hr = hval(L, r);
         const double rpr = gx_row(L, L.dz, xw, r) - hr;
-        L.rp[r] = rpr;
-        const double sar = L.sa[r];
-        double y = L.la[r];
+        A.rp(k, r) = rpr;
+        const double sar = A.sa(k, r);
+        double y = A.la(k, r);
         if (sar != 0.0) {
             y = y + rpr * idl;
-            L.la[r] = y;
+            A.la(k, r) = y;
             yneg = fmax(yneg, -y);
         } else {
             viol = fmax(viol, rpr);
@@ -2417,7 +2564,8 @@ __device__ __forceinline__ D4 polish_dual_body(const cParams& P, const LT& L) {
         // the next refinement's tv = mask (h / delta - y) (polish_rhs_body), formed here
         // in the row's own thread: its pass and barrier leave the multiplier iteration
         L.tv[r] = sar * (hr * idl - y);
-    }
+    });
+    A.template store<RV_RP | RV_LA>();   // read by ph_polish_accept and the next refinement
     double dmax = 0.0, xmax = 0.0;
     for (int e = threadIdx.x; e < L.n; e += NT) {
         const double x = L.dz[e];
@@ -2433,7 +2581,9 @@ __device__ __forceinline__ D4 polish_dual_body(const cParams& P, const LT& L) {
 // ends the refinement here, the next right-hand side in the same call
 PHASE D4 ph_polish_dual_next(Ctx c, int ref, int cap, double early) {
     LAYDEF;
-    const D4 d = polish_dual_body(P, L);
+    ROWSDEF;
+    A.template load<RV_SA | RV_LA>();
+    const D4 d = polish_dual_body(P, L, A);
     if (polish_stop(d, ref, early) == 0 && ref + 1 < cap) rhs_from_tv_body(P, L, P.polRho);
     return d;
 }

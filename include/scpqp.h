@@ -106,6 +106,8 @@ typedef struct scpqp_batch_in {
     const double* u_warm;    /* [B][n_veh*hp_b] prevOutput['u'] (vehicle-major), or NULL*/
     int32_t max_scp_iter;    /* 0: handle default; else override (e.g. 1 = one QP)     */
     int32_t reserved;
+    const int32_t* variant;  /* [B]             per-problem entry of the handle's parameter
+                                table (scpqp_variants.h), or NULL (= entry 0)          */
 } scpqp_batch_in;
 
 /* per-call outputs of scpqp_solve (DEVICE pointers; any may be NULL) */

@@ -25,7 +25,10 @@
 
 #include <math.h>
 
+#include <vector>
+
 #include "scpqp_metrics.h"
+#include "scpqp_variants.h"
 
 int scpqp_fail_(int code, const char* msg);   // scpqp.hip: sets scpqp_last_error()
 
@@ -128,7 +131,8 @@ __device__ __forceinline__ double wave_min(double x) {
     return x;
 }
 
-__global__ __launch_bounds__(WAVE) void metrics_kernel(const DevConst* __restrict__ P, int n_ticks,
+__global__ __launch_bounds__(WAVE) void metrics_kernel(const DevConst* __restrict__ table, int n_var,
+                                                       const int* __restrict__ variant, int n_ticks,
                                                        int tick0, int k_first,
                                                        const double* __restrict__ x_path,
                                                        scpqp_metrics_acc acc, bool have_acc,
@@ -140,6 +144,11 @@ __global__ __launch_bounds__(WAVE) void metrics_kernel(const DevConst* __restric
 
     const int lane = threadIdx.x;
     const size_t b = blockIdx.x;
+    // the realisation's constants; an index outside the table leaves the realisation's
+    // accumulator and dense outputs untouched (the whole workgroup leaves: b is uniform)
+    const int var = variant ? variant[b] : 0;
+    if (var < 0 || var >= n_var) return;
+    const DevConst* __restrict__ P = table + var;
     const int nV = P->n_veh, nO = P->n_obst, nP = P->n_pair, K = n_ticks + 1;
     const int nVO = nV * nO;
     const int chunk = ENT_CAP / nV;         // ticks per chunk (>= 42)
@@ -305,41 +314,43 @@ int launched() {
 struct scpqp_metrics {
     int device;
     int n_veh, n_obst, n_pair;
-    DevConst* dev;
+    DevConst* dev;        // the constants table: n_var blocks (scpqp_metrics_set_variants)
+    int n_var;
+    double tick_length;
 };
 
-extern "C" {
+namespace {
 
-int scpqp_metrics_create(const scpqp_metrics_params* p, int device, scpqp_metrics** out) {
-    if (!p || !out) return scpqp_fail_(SCPQP_E_ARG, "null argument");
-    *out = nullptr;
+// the checks of one scpqp_metrics_params that need no other state (create, set_variants)
+int check_params(const scpqp_metrics_params* p) {
     if (p->n_veh < 1 || p->n_veh > MAXV) return scpqp_fail_(SCPQP_E_ARG, "n_veh out of range");
     if (p->n_obst < 0 || p->n_obst > MAXO) return scpqp_fail_(SCPQP_E_ARG, "n_obst out of range");
     if (p->ref_max_pts < 2 || p->ref_max_pts > MAXP)
         return scpqp_fail_(SCPQP_E_ARG, "ref_max_pts out of range");
     if (!(p->tick_length > 0.0) || isinf(p->tick_length))
         return scpqp_fail_(SCPQP_E_ARG, "tick_length must be finite and > 0");
-    if (device < 0) return scpqp_fail_(SCPQP_E_ARG, "device < 0");
+    return 0;
+}
+
+// The device constants of one scpqp_metrics_params (checked by check_params): what
+// create uploads, and entry k of the table scpqp_metrics_set_variants installs.
+int fill_const(const scpqp_metrics_params* p, DevConst* c) {
     if (!p->length || !p->width || !p->dsafe_veh || !p->ref_polyline || !p->ref_npts)
         return scpqp_fail_(SCPQP_E_ARG, "null array");
     if (p->n_obst > 0 && (!p->dsafe_obs || !p->obstacles))
         return scpqp_fail_(SCPQP_E_ARG, "null obstacle array");
     const int nV = p->n_veh, nO = p->n_obst;
-    DevConst* c = new DevConst();
+    *c = DevConst();
     c->n_veh = nV;
     c->n_obst = nO;
     c->n_pair = nV * (nV - 1) / 2;
     c->tick_length = p->tick_length;
     for (int v = 0; v < nV; ++v) {
         if (!(p->length[v] >= 0.0) || !(p->width[v] >= 0.0) || isinf(p->length[v]) ||
-            isinf(p->width[v])) {
-            delete c;
+            isinf(p->width[v]))
             return scpqp_fail_(SCPQP_E_ARG, "length / width must be finite and >= 0");
-        }
-        if (p->ref_npts[v] < 2 || p->ref_npts[v] > p->ref_max_pts) {
-            delete c;
+        if (p->ref_npts[v] < 2 || p->ref_npts[v] > p->ref_max_pts)
             return scpqp_fail_(SCPQP_E_ARG, "ref_npts must be in 2..ref_max_pts");
-        }
         c->hx[v] = p->length[v] / 2;
         c->hy[v] = p->width[v] / 2;
         c->npts[v] = p->ref_npts[v];
@@ -357,7 +368,24 @@ int scpqp_metrics_create(const scpqp_metrics_params* p, int device, scpqp_metric
             c->pair_v[q] = (unsigned char)v;
             c->pair_w[q] = (unsigned char)w;
         }
-    scpqp_metrics* m = new scpqp_metrics{device, nV, nO, c->n_pair, nullptr};
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int scpqp_metrics_create(const scpqp_metrics_params* p, int device, scpqp_metrics** out) {
+    if (!p || !out) return scpqp_fail_(SCPQP_E_ARG, "null argument");
+    *out = nullptr;
+    if (int rc = check_params(p)) return rc;
+    if (device < 0) return scpqp_fail_(SCPQP_E_ARG, "device < 0");
+    DevConst* c = new DevConst();
+    if (int rc = fill_const(p, c)) {
+        delete c;
+        return rc;
+    }
+    scpqp_metrics* m = new scpqp_metrics{device, p->n_veh, p->n_obst, c->n_pair, nullptr, 1, p->tick_length};
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipMalloc(&m->dev, sizeof(DevConst));
     if (e == hipSuccess) e = hipMemcpy(m->dev, c, sizeof(DevConst), hipMemcpyHostToDevice);
@@ -369,6 +397,37 @@ int scpqp_metrics_create(const scpqp_metrics_params* p, int device, scpqp_metric
                            hipGetErrorString(e));
     }
     *out = m;
+    return 0;
+}
+
+int scpqp_metrics_set_variants(scpqp_metrics* m, int32_t n, const scpqp_metrics_params* params) {
+    if (!params) return scpqp_fail_(SCPQP_E_ARG, "null params");
+    if (n < 1) return scpqp_fail_(SCPQP_E_ARG, "n < 1: a table holds at least one variant");
+    if (!m) return scpqp_fail_(SCPQP_E_ARG, "null metrics handle");
+    std::vector<DevConst> table((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        const scpqp_metrics_params* p = &params[k];
+        if (int rc = check_params(p)) return rc;
+        if (p->n_veh != m->n_veh) return scpqp_fail_(SCPQP_E_ARG, "variant differs from the handle in n_veh");
+        if (p->n_obst != m->n_obst) return scpqp_fail_(SCPQP_E_ARG, "variant differs from the handle in n_obst");
+        if (p->tick_length != m->tick_length)
+            return scpqp_fail_(SCPQP_E_ARG, "variant differs from the handle in tick_length");
+        if (int rc = fill_const(p, &table[k])) return rc;
+    }
+    // launches in flight read the old table: wait for them before it is freed
+    hipError_t e = hipSetDevice(m->device);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    DevConst* dev = nullptr;
+    if (e == hipSuccess) e = hipMalloc(&dev, sizeof(DevConst) * (size_t)n);
+    if (e == hipSuccess) e = hipMemcpy(dev, table.data(), sizeof(DevConst) * (size_t)n, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (dev) (void)hipFree(dev);
+        return scpqp_fail_(e == hipErrorOutOfMemory ? SCPQP_E_NOMEM : SCPQP_E_HIP,
+                           hipGetErrorString(e));
+    }
+    (void)hipFree(m->dev);
+    m->dev = dev;
+    m->n_var = n;
     return 0;
 }
 
@@ -397,6 +456,15 @@ int scpqp_metrics_reset(scpqp_metrics* m, int32_t B, const scpqp_metrics_acc* ac
 int scpqp_metrics_accumulate(scpqp_metrics* m, int32_t B, int32_t n_ticks, int32_t tick0,
                              int32_t k_first, const double* x_path, const scpqp_metrics_acc* acc,
                              const scpqp_metrics_dense* dense, void* stream) {
+    return scpqp_metrics_accumulate_variants(m, B, n_ticks, tick0, k_first, x_path, acc, dense,
+                                             nullptr, stream);
+}
+
+int scpqp_metrics_accumulate_variants(scpqp_metrics* m, int32_t B, int32_t n_ticks, int32_t tick0,
+                                      int32_t k_first, const double* x_path,
+                                      const scpqp_metrics_acc* acc,
+                                      const scpqp_metrics_dense* dense, const int32_t* variant,
+                                      void* stream) {
     if (B < 0 || n_ticks < 0) return scpqp_fail_(SCPQP_E_ARG, "batch size / n_ticks < 0");
     if (tick0 < 0) return scpqp_fail_(SCPQP_E_ARG, "tick0 < 0");
     if (k_first != 0 && k_first != 1) return scpqp_fail_(SCPQP_E_ARG, "k_first must be 0 or 1");
@@ -421,7 +489,8 @@ int scpqp_metrics_accumulate(scpqp_metrics* m, int32_t B, int32_t n_ticks, int32
     const scpqp_metrics_acc a = acc ? *acc : scpqp_metrics_acc{};
     const scpqp_metrics_dense d = dense ? *dense : scpqp_metrics_dense{};
     hipLaunchKernelGGL(metrics_kernel, dim3((unsigned)B), dim3(WAVE), 0,
-                       static_cast<hipStream_t>(stream), m->dev, n_ticks, tick0, k_first, x_path, a,
+                       static_cast<hipStream_t>(stream), m->dev, m->n_var, variant, n_ticks, tick0, k_first,
+                       x_path, a,
                        acc != nullptr, d);
     return launched();
 }

@@ -4,6 +4,7 @@
 // so the library builds in parallel) and declared extern below.
 
 #include "scpqp_kernel.h"
+#include "scpqp_variants.h"
 
 #include <vector>
 
@@ -87,7 +88,8 @@ int fail(int code, const char* fmt, const char* detail = "") {
 struct scpqp_handle {
     scpqp_dims dims;
     DevParams hostP;
-    DevParams* devP = nullptr;
+    DevParams* devP = nullptr;   // the parameter table: nVar blocks (scpqp_set_variants)
+    int nVar = 1;
     int device = 0;
     int cus = 256;
     int* counter = nullptr;
@@ -223,6 +225,7 @@ int launch(scpqp_handle* h, KArgs& a, hipStream_t st) {
         }
     }
     a.P = h->devP;
+    a.nVar = h->nVar;
     a.ws = h->ws;
     a.wsStride = h->wsStride;
     a.counter = h->counter;
@@ -302,42 +305,31 @@ KArgs base_args(int32_t B, const scpqp_batch_in* in) {
     a.refIn = in->ref_points;
     a.uWarm = in->u_warm;
     a.hp = in->hp;
+    a.variant = in->variant;
     a.maxScp = in->max_scp_iter;
     return a;
 }
 
-}  // namespace
-
-// error reporting for the other translation units of the library (plant.hip)
-int scpqp_fail_(int code, const char* msg) { return fail(code, "%s", msg); }
-
-extern "C" {
-
-const char* scpqp_last_error(void) { return g_err; }
-
-const char* scpqp_version(void) { return "scpqp-mi355x 0.4 (gfx950, fp64)"; }
-
-int scpqp_create(const scpqp_dims* dims, const scpqp_params* p, int device, scpqp_handle** out) {
-    if (!dims || !p || !out) return fail(SCPQP_E_ARG, "null argument%s");
-    *out = nullptr;
-    if (dims->n_veh < 1 || dims->n_veh > SCPQP_MAX_VEH) return fail(SCPQP_E_ARG, "n_veh out of range%s");
-    if (dims->n_obst < 0 || dims->n_obst > SCPQP_MAX_OBST) return fail(SCPQP_E_ARG, "n_obst out of range%s");
-    if (dims->hp_max < 1 || dims->hp_max > SCPQP_MAX_HP) return fail(SCPQP_E_ARG, "hp_max out of range%s");
-    if (dims->n_veh * dims->hp_max + 1 > 256) return fail(SCPQP_E_SIZE, "n_veh*hp_max+1 > 256%s");
-    if (dims->max_batch < 0) return fail(SCPQP_E_ARG, "max_batch < 0%s");
+// the pointer checks of one scpqp_params (create and set_variants)
+int check_params(const scpqp_dims& dims, const scpqp_params* p) {
     if (!p->lf || !p->lr || !p->q || !p->q_final || !p->r || !p->dsafe_veh)
         return fail(SCPQP_E_ARG, "null per-vehicle parameter%s");
-    if (dims->n_obst > 0 && !p->dsafe_obs) return fail(SCPQP_E_ARG, "n_obst > 0 needs dsafe_obs%s");
+    if (dims.n_obst > 0 && !p->dsafe_obs) return fail(SCPQP_E_ARG, "n_obst > 0 needs dsafe_obs%s");
     if (p->ref_max_pts > SCPQP_MAX_REFPTS) return fail(SCPQP_E_ARG, "ref_max_pts too large%s");
-    scpqp_handle* h = new (std::nothrow) scpqp_handle();
-    if (!h) return fail(SCPQP_E_NOMEM, "out of host memory%s");
-    h->dims = *dims;
-    h->device = device;
-    DevParams& P = h->hostP;
+    const int mp = p->ref_max_pts > 0 ? p->ref_max_pts : 2;
+    for (int v = 0; p->ref_npts && v < dims.n_veh; ++v)
+        if (p->ref_npts[v] < 0 || p->ref_npts[v] > mp)
+            return fail(SCPQP_E_ARG, "ref_npts outside 0..ref_max_pts%s");
+    return 0;
+}
+
+// The device parameter block of one scpqp_params (checked by check_params): what create
+// uploads, and entry k of the table scpqp_set_variants installs.
+void fill_block(const scpqp_dims& dims, const scpqp_params* p, DevParams& P) {
     memset(&P, 0, sizeof(P));
-    const int V = dims->n_veh, O = dims->n_obst;
+    const int V = dims.n_veh, O = dims.n_obst;
     P.nV = V;
-    P.hpMax = dims->hp_max;
+    P.hpMax = dims.hp_max;
     P.nO = O;
     P.maxPts = p->ref_max_pts > 0 ? p->ref_max_pts : 2;
     P.maxScp = p->max_scp_iter > 0 ? p->max_scp_iter : 20;
@@ -373,6 +365,51 @@ int scpqp_create(const scpqp_dims* dims, const scpqp_params* p, int device, scpq
             P.poly[(v * P.maxPts + i) * 2 + 1] = p->ref_polyline[(v * p->ref_max_pts + i) * 2 + 1];
         }
     }
+}
+
+// the field of a variant's block that differs from the handle's and may not, or null
+const char* fixed_field_differs(const DevParams& a, const DevParams& b) {
+    if (a.dt != b.dt) return "dt";
+    if (a.uLim != b.uLim) return "u_lim";
+    if (a.ctol != b.ctol) return "constraint_tol";
+    if (a.deltaTol != b.deltaTol) return "delta_tol";
+    if (a.slackW != b.slackW) return "slack_weight";
+    if (a.maxScp != b.maxScp) return "max_scp_iter";
+    if (a.maxIpm != b.maxIpm) return "max_ipm_iter";
+    if (a.nRefine != b.nRefine) return "polish_refine";
+    if (a.flags != b.flags) return "flags";
+    if (a.ipmTol != b.ipmTol) return "ipm_tol";
+    if (a.polDelta != b.polDelta) return "polish_delta";
+    if (a.polRho != b.polRho) return "polish_rho";
+    return nullptr;
+}
+
+}  // namespace
+
+// error reporting for the other translation units of the library (plant.hip)
+int scpqp_fail_(int code, const char* msg) { return fail(code, "%s", msg); }
+
+extern "C" {
+
+const char* scpqp_last_error(void) { return g_err; }
+
+const char* scpqp_version(void) { return "scpqp-mi355x 0.4 (gfx950, fp64)"; }
+
+int scpqp_create(const scpqp_dims* dims, const scpqp_params* p, int device, scpqp_handle** out) {
+    if (!dims || !p || !out) return fail(SCPQP_E_ARG, "null argument%s");
+    *out = nullptr;
+    if (dims->n_veh < 1 || dims->n_veh > SCPQP_MAX_VEH) return fail(SCPQP_E_ARG, "n_veh out of range%s");
+    if (dims->n_obst < 0 || dims->n_obst > SCPQP_MAX_OBST) return fail(SCPQP_E_ARG, "n_obst out of range%s");
+    if (dims->hp_max < 1 || dims->hp_max > SCPQP_MAX_HP) return fail(SCPQP_E_ARG, "hp_max out of range%s");
+    if (dims->n_veh * dims->hp_max + 1 > 256) return fail(SCPQP_E_SIZE, "n_veh*hp_max+1 > 256%s");
+    if (dims->max_batch < 0) return fail(SCPQP_E_ARG, "max_batch < 0%s");
+    if (const int rc = check_params(*dims, p)) return rc;
+    scpqp_handle* h = new (std::nothrow) scpqp_handle();
+    if (!h) return fail(SCPQP_E_NOMEM, "out of host memory%s");
+    h->dims = *dims;
+    h->device = device;
+    DevParams& P = h->hostP;
+    fill_block(*dims, p, P);
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e == hipSuccess) e = hipMalloc(&h->devP, sizeof(DevParams));
@@ -402,6 +439,34 @@ int scpqp_destroy(scpqp_handle* h) {
     if (h->perm) (void)hipFree(h->perm);
     if (h->ws) (void)hipFree(h->ws);
     delete h;
+    return 0;
+}
+
+int scpqp_set_variants(scpqp_handle* h, int32_t n, const scpqp_params* params) {
+    if (!params) return fail(SCPQP_E_ARG, "null params%s");
+    if (n < 1) return fail(SCPQP_E_ARG, "n < 1: a table holds at least one variant%s");
+    if (!h) return fail(SCPQP_E_ARG, "null handle%s");
+    std::vector<DevParams> table((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        if (const int rc = check_params(h->dims, &params[k])) return rc;
+        fill_block(h->dims, &params[k], table[k]);
+        if (const char* f = fixed_field_differs(table[k], h->hostP))
+            return fail(SCPQP_E_ARG, "variant differs from the handle in %s", f);
+    }
+    // launches in flight read the old table: wait for them before it is freed
+    DevParams* dev = nullptr;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMalloc(&dev, sizeof(DevParams) * (size_t)n));
+    const hipError_t e = hipMemcpy(dev, table.data(), sizeof(DevParams) * (size_t)n, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(dev);
+        return fail(SCPQP_E_HIP, "HIP error: %s", hipGetErrorString(e));
+    }
+    (void)hipFree(h->devP);
+    h->devP = dev;
+    h->nVar = n;
+    h->hostP = table[0];
     return 0;
 }
 

@@ -125,8 +125,8 @@ struct DevParams {
 enum Mode { MODE_SOLVE = 0, MODE_LINEARIZE = 1, MODE_EVALUATE = 2, MODE_SAMPLE = 3 };
 
 struct KArgs {
-    const DevParams* P;
-    int B, mode, maxScp, pad0;
+    const DevParams* P;   // the parameter table: nVar blocks, entry 0 holds the sizes
+    int B, mode, maxScp, nVar;
     const double *x0, *u0, *ec, *obst, *refIn, *uWarm, *uEval;
     const int* hp;
     double *uOut, *trajOut, *obj, *maxv, *sumv;
@@ -138,6 +138,7 @@ struct KArgs {
     long long wsStride;
     int* counter;
     const int* perm;   // optional: work item w -> problem perm[w] (longest horizons first)
+    const int* variant;   // optional: problem b uses table entry variant[b] (else entry 0)
 };
 // The kernel argument block, addressed in the constant (kernarg) address space:
 // out-of-line functions take it by pointer without the copy to private memory
@@ -885,14 +886,15 @@ __device__ int setup_problem(const cKArgs& a, const cParams& P, const LT& L, int
 // Out-of-line setup: the trigonometry and expm constants stay out of the
 // register allocation of the solve loop.
 template <bool HG, bool VG, int RM, int OCC, int SH>
-__device__ __noinline__ int setup_problem_ni(const cKArgs* ap, gdouble* ws, int b, int Hb) {
+__device__ __noinline__ int setup_problem_ni(const cKArgs* ap, const cParams* Pp, gdouble* ws, int b, int Hb) {
     // uniform arguments arrive in VGPRs: back to SGPRs (see uniform_ctx)
     ap = (const cKArgs*)readfirstlane_u64((unsigned long long)ap);
+    Pp = (const cParams*)readfirstlane_u64((unsigned long long)Pp);
     ws = (gdouble*)readfirstlane_u64((unsigned long long)ws);
     b = __builtin_amdgcn_readfirstlane(b);
     Hb = __builtin_amdgcn_readfirstlane(Hb);
     const cKArgs& a = *ap;
-    const cParams& P = *(const cParams*)a.P;
+    const cParams& P = *Pp;   // the problem's variant (the sizes equal entry 0's)
     const Off f = plan_offsets(shapeV<SH>(P.nV), shapeO<SH>(P.nO), shapeHM<SH>(P.hpMax), HG, VG, lean_plan(HG, VG, OCC));
     const Lay<HG, VG, RM, OCC> L = make_lay<HG, VG, RM, OCC, SH>((ldouble*)smem_, ws, f, P.nV, P.nO, Hb);
     return setup_problem(a, P, L, b);
@@ -2880,10 +2882,10 @@ __device__ __forceinline__ int lead_wave_elect(lint* sh) {
 template <bool HG, bool VG, int RM, int OCC, int SH>
 __global__ __launch_bounds__(NT, OCC) void scp_kernel(KArgs a) {
     ldouble* smem = (ldouble*)smem_;
-    const cParams& P = *(const cParams*)a.P;
+    const cParams& P0 = *(const cParams*)a.P;   // entry 0: the sizes every variant shares
     const int tid = threadIdx.x;
     gdouble* ws = a.ws ? (gdouble*)a.ws + (size_t)blockIdx.x * a.wsStride : nullptr;
-    const Off f = plan_offsets(shapeV<SH>(P.nV), shapeO<SH>(P.nO), shapeHM<SH>(P.hpMax), HG, VG, lean_plan(HG, VG, OCC));
+    const Off f = plan_offsets(shapeV<SH>(P0.nV), shapeO<SH>(P0.nO), shapeHM<SH>(P0.hpMax), HG, VG, lean_plan(HG, VG, OCC));
     lint* slot = (lint*)(smem + f.red + kWorkSlot);
     lint* orslot = (lint*)(smem + f.red + kOrSlot);
     ldouble* lub = smem + f.ub;   // u-bar
@@ -2904,8 +2906,10 @@ __global__ __launch_bounds__(NT, OCC) void scp_kernel(KArgs a) {
         const int b = __builtin_amdgcn_readfirstlane(slot[0]);
         bar();
         if (b >= a.B) break;
-        const int Hb = __builtin_amdgcn_readfirstlane(a.hp ? a.hp[b] : P.hpMax);
-        if (Hb < 1 || Hb > P.hpMax) {   // horizon outside the slot: report, never index with it
+        const int Hb = __builtin_amdgcn_readfirstlane(a.hp ? a.hp[b] : P0.hpMax);
+        const int var = __builtin_amdgcn_readfirstlane(a.variant ? a.variant[b] : 0);
+        // horizon outside the slot or variant outside the table: report, never index with it
+        if (Hb < 1 || Hb > P0.hpMax || var < 0 || var >= a.nVar) {
             if (tid == 0) {
                 if (a.status) a.status[b] = SCPQP_ST_INVALID;
                 if (a.nscp) a.nscp[b] = 0;
@@ -2917,7 +2921,10 @@ __global__ __launch_bounds__(NT, OCC) void scp_kernel(KArgs a) {
             bar();
             continue;
         }
-        const Ctx c{(const cParams*)a.P, ws, Hb, lead};
+        // the problem's parameter block: a wave-uniform base in the constant address space
+        const cParams* Pp = (const cParams*)a.P + var;
+        const cParams& P = *Pp;
+        const Ctx c{Pp, ws, Hb, lead};
         const int V = P.nV, N = V * Hb, O = P.nO;
 #ifdef SCPQP_PROF
         if (tid == 0 && b < 8192) g_ptime[2 * b] = __builtin_amdgcn_s_memrealtime();
@@ -2926,7 +2933,7 @@ __global__ __launch_bounds__(NT, OCC) void scp_kernel(KArgs a) {
         // the sampler's flags, ORed over the workgroup in an LDS slot (__syncthreads_or
         // would add 256 B of static LDS to every plan)
         if (tid == 0) *orslot = 0;
-        const int sflag = setup_problem_ni<HG, VG, RM, OCC, SH>((const cKArgs*)__builtin_amdgcn_kernarg_segment_ptr(), ws, b, Hb);
+        const int sflag = setup_problem_ni<HG, VG, RM, OCC, SH>((const cKArgs*)__builtin_amdgcn_kernarg_segment_ptr(), Pp, ws, b, Hb);
         PROF_ACC(10);
         if (sflag) *orslot = 1;
         bar();

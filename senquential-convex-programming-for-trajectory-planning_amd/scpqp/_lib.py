@@ -1,5 +1,5 @@
-"""ctypes binding of ``include/scpqp.h``, ``include/scpqp_noise.h`` and
-``include/scpqp_metrics.h`` (the C-ABI of the HIP library).
+"""ctypes binding of ``include/scpqp.h``, ``include/scpqp_noise.h``,
+``include/scpqp_metrics.h`` and ``include/scpqp_variants.h`` (the C-ABI of the HIP library).
 
 The shared library ``libscpqp.so`` is built in-tree (``__graft_entry__.build()``
 or ``python -m scpqp.build``).  There is no CPU fallback: if the library or a
@@ -51,7 +51,8 @@ class Params(C.Structure):
 class BatchIn(C.Structure):
     _fields_ = [("x0", C.c_void_p), ("u0", C.c_void_p), ("ec_noise", C.c_void_p),
                 ("hp", C.c_void_p), ("obst", C.c_void_p), ("ref_points", C.c_void_p),
-                ("u_warm", C.c_void_p), ("max_scp_iter", C.c_int32), ("reserved", C.c_int32)]
+                ("u_warm", C.c_void_p), ("max_scp_iter", C.c_int32), ("reserved", C.c_int32),
+                ("variant", C.c_void_p)]
 
 
 class BatchOut(C.Structure):
@@ -124,6 +125,10 @@ class MetricsDense(C.Structure):
 METRICS_EXPORTS = ("scpqp_metrics_create", "scpqp_metrics_destroy", "scpqp_metrics_reset",
                    "scpqp_metrics_accumulate")
 
+# every symbol include/scpqp_variants.h declares (checked by tests/test_variants_host.py)
+VARIANT_EXPORTS = ("scpqp_set_variants", "scpqp_metrics_set_variants",
+                   "scpqp_metrics_accumulate_variants")
+
 _lib = None
 
 
@@ -190,6 +195,16 @@ def load(path=None):
     lib.scpqp_metrics_accumulate.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, V, MA,
                                              MD, V]
     lib.scpqp_metrics_accumulate.restype = C.c_int
+    # an explicit ``path`` may name an A/B build from before the variants (tools/gpu.sh ab):
+    # it is bound without them, and calling one there raises AttributeError
+    if path is None or hasattr(lib, "scpqp_set_variants"):
+        lib.scpqp_set_variants.argtypes = [H, C.c_int32, C.POINTER(Params)]
+        lib.scpqp_set_variants.restype = C.c_int
+        lib.scpqp_metrics_set_variants.argtypes = [H, C.c_int32, C.POINTER(MetricsParams)]
+        lib.scpqp_metrics_set_variants.restype = C.c_int
+        lib.scpqp_metrics_accumulate_variants.argtypes = [H, C.c_int32, C.c_int32, C.c_int32,
+                                                          C.c_int32, V, MA, MD, V, V]
+        lib.scpqp_metrics_accumulate_variants.restype = C.c_int
     if path is None:
         _lib = lib
     return lib

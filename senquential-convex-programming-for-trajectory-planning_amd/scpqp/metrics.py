@@ -6,6 +6,7 @@
                  margin to the planner's ``dsafe`` and the cross-track error to the
                  reference polylines, along the path the plant really drove at tick
                  resolution.  It holds O(B * nVeh) state for a whole run: no kept paths.
+``summarize_by_variant``  the same per scenario variant of a sweep.
 ``summarize``    batch summary of one or several result dicts as plain Python numbers
                  (collision rate with its Wilson 95 % interval, clearance quantiles,
                  cross-track RMS and maximum).
@@ -73,7 +74,7 @@ class PathMetrics:
     """Scenario-bound accumulator of realised-path metrics for up to ``max_batch``
     realisations on one GPU."""
 
-    def __init__(self, scenario, max_batch, device=None):
+    def __init__(self, scenario, max_batch, device=None, variants=None):
         if not torch.cuda.is_available():
             raise RuntimeError("scpqp: no GPU visible; the HIP path has no CPU fallback")
         self.lib = LB.load()
@@ -101,6 +102,24 @@ class PathMetrics:
                     for k, s in shapes.items()}
         self._acc = LB.MetricsAcc(**{k: self.acc[k].data_ptr() for k in LB.METRICS_ACC_FIELDS})
         self.B = 0
+        self.n_variants = 1
+        if variants is not None:
+            self.set_variants(variants)
+
+    def set_variants(self, scenarios):
+        """Install the scenarios as the handle's table of constants
+        (``scpqp_metrics_set_variants``): realisation b of ``accumulate(..., variant=)`` is
+        measured against ``scenarios[variant[b]]``.  Footprints, dsafe tables, obstacles and
+        polylines may differ; nVeh, nObst and tick_length are the handle's."""
+        scenarios = list(scenarios)
+        if not scenarios:
+            raise ValueError("set_variants needs at least one scenario")
+        packed = [pack_params(sc) for sc in scenarios]
+        table = (LB.MetricsParams * len(packed))(*[P for P, _ in packed])
+        with torch.cuda.device(self.device):
+            LB.check(self.lib.scpqp_metrics_set_variants(self.h, len(packed), table), self.lib)
+        del packed
+        self.n_variants = len(scenarios)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -114,12 +133,15 @@ class PathMetrics:
         LB.check(self.lib.scpqp_metrics_reset(self.h, B, C.byref(self._acc), self._stream()),
                  self.lib)
 
-    def accumulate(self, x_path, tick0, k_first, dense=False):
+    def accumulate(self, x_path, tick0, k_first, dense=False, variant=None):
         """Merge one step's path ``x_path`` [B, nVeh, K, 6] (a float64 device tensor, the
         output of ``plant.plant_step``; entry k is global tick ``tick0 + k``) over its
         entries ``k_first..K-1``.  ``dense=True`` also returns this call's ``gap_veh``
         [B, K, n_pair], ``gap_obs`` [B, K, nVeh, nObst] and ``xtrack`` [B, K, nVeh], over
-        every entry; ``dense="only"`` returns them and leaves the accumulator alone."""
+        every entry; ``dense="only"`` returns them and leaves the accumulator alone.
+        ``variant`` [B] int: realisation b is measured against entry ``variant[b]`` of the
+        table of ``set_variants`` (None: entry 0); with an index outside the table the
+        realisation's accumulator and dense rows are left as they are."""
         if x_path.dtype != torch.float64 or x_path.device != self.device or x_path.dim() != 4:
             raise ValueError("x_path must be a float64 [B, nVeh, K, 6] tensor on the metrics' device")
         B, V, K, nx = (int(s) for s in x_path.shape)
@@ -128,6 +150,11 @@ class PathMetrics:
         if dense != "only" and B != self.B:
             raise ValueError(f"x_path holds {B} realisations, reset() was called for {self.B}")
         x = x_path.contiguous()
+        var = None
+        if variant is not None:
+            var = torch.as_tensor(variant, device=self.device).to(torch.int32).contiguous()
+            if var.numel() != B:
+                raise ValueError(f"variant [B]: expected {B} elements, got {var.numel()}")
         out, D = None, None
         if dense:
             f = dict(dtype=torch.float64, device=self.device)
@@ -137,10 +164,17 @@ class PathMetrics:
             D = LB.MetricsDense(gap_veh=out["gap_veh"].data_ptr() if self.n_pair else None,
                                 gap_obs=out["gap_obs"].data_ptr() if self.nO else None,
                                 xtrack=out["xtrack"].data_ptr())
-        LB.check(self.lib.scpqp_metrics_accumulate(
-            self.h, B, K - 1, int(tick0), int(k_first), C.c_void_p(x.data_ptr()),
-            None if dense == "only" else C.byref(self._acc), None if D is None else C.byref(D),
-            self._stream()), self.lib)
+        acc = None if dense == "only" else C.byref(self._acc)
+        if var is None:
+            LB.check(self.lib.scpqp_metrics_accumulate(
+                self.h, B, K - 1, int(tick0), int(k_first), C.c_void_p(x.data_ptr()), acc,
+                None if D is None else C.byref(D), self._stream()), self.lib)
+        else:
+            LB.check(self.lib.scpqp_metrics_accumulate_variants(
+                self.h, B, K - 1, int(tick0), int(k_first), C.c_void_p(x.data_ptr()), acc,
+                None if D is None else C.byref(D), C.c_void_p(var.data_ptr()), self._stream()),
+                self.lib)
+            self._last_variant = var   # alive until the stream has consumed it
         return out
 
     def result(self):
@@ -216,3 +250,21 @@ def summarize(results):
         "xtrack_max": float(xmax.max()),
     }
     return out
+
+
+def summarize_by_variant(results, variant_of):
+    """``{variant: summarize(...)}`` over the realisations of each variant.  ``results``: one
+    result dict or a list of them (concatenated, as ``summarize`` does); ``variant_of``: the
+    variant index of every realisation, in the same order."""
+    if isinstance(results, dict):
+        results = [results]
+    if not results:
+        raise ValueError("no results")
+    var = np.asarray(variant_of.cpu() if hasattr(variant_of, "cpu") else variant_of).reshape(-1)
+    merged = {k: np.concatenate([np.asarray(r[k].cpu() if hasattr(r[k], "cpu") else r[k])
+                                 for r in results], axis=0) for k in results[0]}
+    n = int(merged["first_collision_tick"].shape[0])
+    if var.shape[0] != n:
+        raise ValueError(f"variant_of holds {var.shape[0]} entries for {n} realisations")
+    return {int(k): summarize({f: a[var == k] for f, a in merged.items()})
+            for k in np.unique(var)}

@@ -43,35 +43,45 @@ CONSTRAINT_TOL = 2 * 2.1 * 1e-3   # Config.py:18
 
 
 def evaluate_in_original_problem(scenario, U, traj, ref_points, obst_future=None,
-                                 tol=CONSTRAINT_TOL):
+                                 tol=CONSTRAINT_TOL, variants=None, variant_of=None):
     """SCPcontroller.evaluateInOriginalProblem (SCP_controller.py:343-400) for a
     batch, on the device: U [B, Hp, nVeh] (the clipped controller output),
     traj [B, Hp, 2, nVeh] (trajectory prediction), ref_points [B, Hp, 2, nVeh],
     obst_future [B, nObst, 2, Hp] or None.  Returns tensors: the objective terms
     [B], constraint values [B, nVeh, nVeh, Hp] / [B, nVeh, nObst, Hp] and
-    predictionFeasible [B] (from the predicted trajectory, as the reference)."""
+    predictionFeasible [B] (from the predicted trajectory, as the reference).
+    With ``variants`` (a list of scenarios) and ``variant_of`` (an integer device tensor
+    [B]), realisation b is weighed with the Q, Q_final, R and dsafe tables of
+    ``variants[variant_of[b]]`` instead of ``scenario``'s."""
     dev = U.device
     f = dict(dtype=torch.float64, device=dev)
     nV = U.shape[2]
-    Q = torch.tensor([float(q) for q in scenario.Q], **f)
-    Qf = torch.tensor([float(q) for q in scenario.Q_final], **f)
-    Rw = torch.tensor([float(r) for r in scenario.R], **f)
+    scs = [scenario] if variants is None else list(variants)
+
+    def table(get):
+        # [1, ...] of the scenario, or [B, ...] gathered per realisation
+        t = torch.as_tensor(np.stack([np.asarray(get(sc), float) for sc in scs]), **f)
+        return t if variants is None else t[variant_of.long()]
+
+    Q = table(lambda sc: [float(q) for q in sc.Q])
+    Qf = table(lambda sc: [float(q) for q in sc.Q_final])
+    Rw = table(lambda sc: [float(r) for r in sc.R])
     err2 = (ref_points - traj) ** 2                                  # [B, Hp, 2, nV]
     objx = (err2[:, :-1].sum(dim=(1, 2)) * Q).sum(-1) + (err2[:, -1].sum(dim=1) * Qf).sum(-1)
     obju = ((U ** 2).sum(dim=1) * Rw).sum(-1)
-    ds2 = torch.as_tensor(np.asarray(scenario.dsafeVehicles, float) ** 2, **f)   # [nV, nV]
+    ds2 = table(lambda sc: np.asarray(sc.dsafeVehicles, float) ** 2)   # [1 | B, nV, nV]
     p = traj.permute(0, 3, 2, 1)                                     # [B, nV, 2, Hp]
     d2 = ((p[:, :, None] - p[:, None, :]) ** 2).sum(3)               # [B, nV, nV, Hp]
-    cv = ds2[None, :, :, None] - d2
+    cv = ds2[:, :, :, None] - d2
     eye = torch.eye(nV, dtype=torch.bool, device=dev)[None, :, :, None]
     cv = torch.where(eye, torch.zeros_like(cv), cv)                  # diagonal stays 0
     viol = (cv > tol).flatten(1).any(1)
     out = dict(predictionObjectiveValueX=objx, predictionObjectiveValueU=obju,
                predictionObjectiveValue=objx + obju, constraintValuesVehicle=cv)
     if obst_future is not None and obst_future.shape[1] > 0:
-        dso = torch.as_tensor(np.asarray(scenario.dsafeObstacles, float) ** 2, **f)  # [nV, nO]
+        dso = table(lambda sc: np.asarray(sc.dsafeObstacles, float).reshape(nV, -1) ** 2)
         d2o = ((p[:, :, None] - obst_future[:, None]) ** 2).sum(3)   # [B, nV, nO, Hp]
-        co = dso[None, :, :, None] - d2o
+        co = dso[:, :, :, None] - d2o
         viol = viol | (co > tol).flatten(1).any(1)
         out["constraintValuesObstacle"] = co
     out["predictionFeasible"] = ~viol
@@ -93,12 +103,52 @@ def held_command_tick(tick_now, tdx, tdu, tps, ticks_total):
     return tick_meas + 1 + (n_path - 1 - lo)
 
 
+# what every variant of a rollout shares with its scenario: the plant kernels, the held
+# command and the per-step tick bookkeeping are computed once for the whole batch
+SHARED_ATTRS = ("Lf", "Lr", "u0", "mechanicalSteeringLimit", "Hp", "dt", "tick_length", "delay_x",
+                "delay_u", "ticks_delay_x", "ticks_delay_u", "ticks_per_sim", "ticks_total", "Nsim")
+
+
+def check_shared(scenario, variants):
+    """ValueError naming the first attribute of SHARED_ATTRS in which a variant differs."""
+    for k, sc in enumerate(variants):
+        for name in SHARED_ATTRS:
+            a, b = getattr(scenario, name), getattr(sc, name)
+            if not np.array_equal(np.asarray(a, float).reshape(-1), np.asarray(b, float).reshape(-1)):
+                raise ValueError(f"variant {k} differs from the scenario in {name}: every "
+                                 f"realisation of a rollout shares it")
+
+
 class ClosedLoopBatch:
     def __init__(self, scenario, B, device=None, h_max=PL.H_MAX, keep_path=False, evaluate=True,
-                 timing=False, trace=False, metrics=False, **solver_kw):
+                 timing=False, trace=False, metrics=False, variants=None, variant_of=None,
+                 **solver_kw):
+        """``variants`` (a list of scenarios) with ``variant_of`` [B]: realisation b runs
+        scenario ``variants[variant_of[b]]``: its solve and metrics parameters, its obstacle
+        set and its evaluation weights.  ``scenario`` supplies what all of them share
+        (SHARED_ATTRS); a variant that differs there is rejected."""
         self.sc = scenario
         self.B = int(B)
         self.device = torch.device(device or "cuda")
+        self.variants = None if variants is None else list(variants)
+        self.variant_of = None
+        if self.variants is None:
+            if variant_of is not None:
+                raise ValueError("variant_of needs variants")
+        else:
+            if variant_of is None:
+                raise ValueError("variants needs variant_of [B]")
+            vo = np.asarray(variant_of.cpu() if isinstance(variant_of, torch.Tensor)
+                            else variant_of).reshape(-1)
+            if vo.shape[0] != self.B:
+                raise ValueError("variant_of must hold B entries")
+            if vo.min() < 0 or vo.max() >= len(self.variants):
+                raise ValueError("variant_of indexes outside variants")
+            check_shared(scenario, self.variants)
+            for k, sc in enumerate(self.variants):
+                if int(sc.nVeh) != int(scenario.nVeh) or int(sc.nObst) != int(scenario.nObst):
+                    raise ValueError(f"variant {k} differs from the scenario in nVeh / nObst")
+            self.variant_of = torch.as_tensor(vo.astype(np.int32), device=self.device)
         self.nV, self.Hp = int(scenario.nVeh), int(scenario.Hp)
         self.tps = int(scenario.ticks_per_sim)
         self.ticks_total = int(scenario.ticks_total)
@@ -112,8 +162,14 @@ class ClosedLoopBatch:
         self.nO = int(scenario.nObst)
         self.obstacles = np.asarray(scenario.obstacles, float).reshape(self.nO, -1) if self.nO \
             else np.zeros((0, 6))
+        # per variant its own obstacle set (result_for_plot draws self.obstacles: variant-free)
+        self.var_obstacles = None
+        if self.variants is not None and self.nO:
+            self.var_obstacles = [np.asarray(sc.obstacles, float).reshape(self.nO, -1)
+                                  for sc in self.variants]
         self.params = PL.plant_params(scenario.Lf, scenario.Lr)
-        self.solver = ScpQpSolver(scenario, max_batch=self.B, device=self.device, **solver_kw)
+        self.solver = ScpQpSolver(scenario, max_batch=self.B, device=self.device,
+                                  variants=self.variants, **solver_kw)
         self.du_lim = float(scenario.mechanicalSteeringLimit) * 2          # Scenarios.py:50
         f = dict(dtype=torch.float64, device=self.device)
         self.L = torch.tensor([float(a) + float(b) for a, b in zip(scenario.Lf, scenario.Lr)], **f)
@@ -128,7 +184,7 @@ class ClosedLoopBatch:
         self.path_metrics = None
         if metrics:
             from .metrics import PathMetrics
-            self.path_metrics = PathMetrics(scenario, self.B, self.device)
+            self.path_metrics = PathMetrics(scenario, self.B, self.device, variants=self.variants)
 
     def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0):
         """main.py:73-75: vehiclePathFullRes[:, v, 0] = x0; the control path holds
@@ -166,10 +222,20 @@ class ClosedLoopBatch:
     def _obstacle_prediction(self, tick_meas):
         """Iter.obstacleFutureTrajectories (MPC_Iter.py:45-51) from the constant-velocity
         obstacle state at the measurement tick (main.py:61-71, 123); the same for every
-        realisation.  Returns a device tensor [B, nObst, 2, Hp] or None."""
+        realisation of a variant.  Returns a device tensor [B, nObst, 2, Hp] or None."""
         if not self.nO:
             return None
-        sc, ob = self.sc, self.obstacles
+        if self.var_obstacles is not None:
+            # one prediction per variant on the host, gathered per realisation on the device
+            fut = np.stack([self._predict(ob, tick_meas) for ob in self.var_obstacles])
+            t = torch.as_tensor(fut, dtype=torch.float64, device=self.device)
+            return t[self.variant_of.long()].contiguous()
+        t = torch.as_tensor(self._predict(self.obstacles, tick_meas), dtype=torch.float64,
+                            device=self.device)
+        return t[None].expand(self.B, -1, -1, -1).contiguous()
+
+    def _predict(self, ob, tick_meas):
+        sc = self.sc
         t_meas = tick_meas * sc.tick_length
         x = t_meas * ob[:, 3] * np.cos(ob[:, 2]) + ob[:, 0]
         y = t_meas * ob[:, 3] * np.sin(ob[:, 2]) + ob[:, 1]
@@ -178,8 +244,7 @@ class ClosedLoopBatch:
         fut = np.zeros((self.nO, 2, self.Hp))
         fut[:, 0] = step * np.cos(ob[:, 2:3]) + x[:, None]
         fut[:, 1] = step * np.sin(ob[:, 2:3]) + y[:, None]
-        t = torch.as_tensor(fut, dtype=torch.float64, device=self.device)
-        return t[None].expand(self.B, -1, -1, -1).contiguous()
+        return fut
 
     def _held_command(self, tick_now):
         return held_command_tick(tick_now, self.tdx, self.tdu, self.tps, self.ticks_total)
@@ -213,7 +278,8 @@ class ClosedLoopBatch:
         u_warm = self.u_prev
         # the draws of comp_jacobian's one ode call (Model.py:58)
         ec_noise = None if rng is None else PL.draw_ec_noise(rng, B, nV, self.device)
-        out = self.solver.solve(x0, u_hold, ec_noise, u_warm=u_warm, obst=obst, out=self.out)
+        out = self.solver.solve(x0, u_hold, ec_noise, u_warm=u_warm, obst=obst, out=self.out,
+                                variant=self.variant_of)
         self.u_prev = out.u.clone()
         if self.timing:
             torch.cuda.synchronize(self.device)
@@ -234,7 +300,8 @@ class ClosedLoopBatch:
                              h_max=self.h_max, device=self.device, rng=rng)
         if self.path_metrics is not None:
             # every global tick once: entry 0 of a later step is the previous step's last
-            self.path_metrics.accumulate(path, tick0=i * tps, k_first=0 if i == 0 else 1)
+            self.path_metrics.accumulate(path, tick0=i * tps, k_first=0 if i == 0 else 1,
+                                         variant=self.variant_of)
         self.last_path = path
         self.state = path[:, :, tps, :].contiguous()
         rec = dict(x0=x0, u0=u_hold, umax=umax, U=U, traj=out.traj.clone(),
@@ -244,10 +311,11 @@ class ClosedLoopBatch:
             rec["epoch"] = i
         if self.evaluate:
             # main.py:201-202: evaluateInOriginalProblem on the clipped U and the prediction
-            ref = self.solver.sample_reference(x0)
+            ref = self.solver.sample_reference(x0, variant=self.variant_of)
             rec["ref"] = ref
             rec["evaluation"] = evaluate_in_original_problem(
-                sc, U.view(B, nV, Hp).transpose(1, 2), rec["traj"], ref, obst)
+                sc, U.view(B, nV, Hp).transpose(1, 2), rec["traj"], ref, obst,
+                variants=self.variants, variant_of=self.variant_of)
         if self.keep_path:
             rec["path"] = path
             rec["delay_traj"] = dtraj

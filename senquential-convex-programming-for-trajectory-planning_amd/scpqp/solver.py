@@ -37,6 +37,50 @@ def _vptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def pack_params(scenario, u_lim=None, max_scp_iter=MAX_SCP_ITER, max_ipm_iter=60, ipm_tol=1e-9,
+                polish_delta=3e-7, polish_rho=1e-12, polish_refine=0, obstacle_quirk=True,
+                warm_start=True):
+    """``scpqp_params`` of a scenario and the arrays its pointers refer to (keep them alive
+    until the library has copied them): the constructor's block and every entry of
+    ``set_variants``."""
+    nV, nO = int(scenario.nVeh), int(scenario.nObst)
+    keep = []
+
+    def arr(x, shape=None, dtype=np.float64):
+        a = np.ascontiguousarray(np.asarray(x, dtype=dtype).reshape(shape if shape else -1))
+        keep.append(a)
+        return a
+
+    lf, lr = arr(scenario.Lf), arr(scenario.Lr)
+    q, qf, r = arr(scenario.Q), arr(scenario.Q_final), arr(scenario.R)
+    dv = arr(scenario.dsafeVehicles, (nV * nV,))
+    do = arr(np.asarray(scenario.dsafeObstacles).reshape(-1) if nO else np.zeros(1))
+    refs = [np.asarray(t, float).reshape(-1, 2) for t in scenario.referenceTrajectories]
+    mp = max(2, max(len(t) for t in refs))
+    if mp > LB.MAX_REFPTS:
+        raise ValueError("reference polyline has too many points")
+    poly = np.zeros((nV, mp, 2))
+    npts = np.zeros(nV, np.int32)
+    for v, t in enumerate(refs):
+        poly[v, :len(t)] = t
+        npts[v] = len(t)
+    poly = arr(poly)
+    npts = arr(npts, dtype=np.int32)
+    P = LB.Params(dt=float(scenario.dt), u_lim=float(scenario.uLim if u_lim is None else u_lim),
+                  dsafe_extra=float(scenario.dsafeExtra),
+                  constraint_tol=CONSTRAINT_TOL, delta_tol=DELTA_TOL, slack_weight=SLACK_WEIGHT,
+                  max_scp_iter=max_scp_iter, max_ipm_iter=max_ipm_iter,
+                  polish_refine=polish_refine,
+                  flags=(LB.FLAG_OBST_QUIRK if obstacle_quirk else 0) |
+                  (0 if warm_start else LB.FLAG_COLD_QP), ipm_tol=ipm_tol,
+                  polish_delta=polish_delta, polish_rho=polish_rho,
+                  lf=_dptr(lf), lr=_dptr(lr), q=_dptr(q), q_final=_dptr(qf), r=_dptr(r),
+                  dsafe_veh=_dptr(dv), dsafe_obs=_dptr(do) if nO else None,
+                  ref_polyline=_dptr(poly), ref_npts=npts.ctypes.data_as(C.POINTER(C.c_int32)),
+                  ref_max_pts=mp)
+    return P, keep
+
+
 @dataclass
 class SolveResult:
     u: torch.Tensor          # [B, nVeh*Hp]  (vehicle-major; problem b uses its first nVeh*hp_b)
@@ -59,7 +103,8 @@ class ScpQpSolver:
 
     def __init__(self, scenario, max_batch, device=None, hp_max=None, u_lim=None,
                  max_scp_iter=MAX_SCP_ITER, max_ipm_iter=60, ipm_tol=1e-9, polish_delta=3e-7,
-                 polish_rho=1e-12, polish_refine=0, obstacle_quirk=True, warm_start=True):
+                 polish_rho=1e-12, polish_refine=0, obstacle_quirk=True, warm_start=True,
+                 variants=None):
         if not torch.cuda.is_available():
             raise RuntimeError("scpqp: no GPU visible; the HIP path has no CPU fallback")
         self.lib = LB.load()
@@ -72,48 +117,42 @@ class ScpQpSolver:
         self.hp_max = int(hp_max or scenario.Hp)
         self.max_batch = int(max_batch)
         nV, nO = self.nV, self.nO
-        self._keep = []
-
-        def arr(x, shape=None, dtype=np.float64):
-            a = np.ascontiguousarray(np.asarray(x, dtype=dtype).reshape(shape if shape else -1))
-            self._keep.append(a)
-            return a
-
-        lf, lr = arr(scenario.Lf), arr(scenario.Lr)
-        q, qf, r = arr(scenario.Q), arr(scenario.Q_final), arr(scenario.R)
-        dv = arr(scenario.dsafeVehicles, (nV * nV,))
-        do = arr(np.asarray(scenario.dsafeObstacles).reshape(-1) if nO else np.zeros(1))
-        refs = [np.asarray(t, float).reshape(-1, 2) for t in scenario.referenceTrajectories]
-        mp = max(2, max(len(t) for t in refs))
-        if mp > LB.MAX_REFPTS:
-            raise ValueError("reference polyline has too many points")
-        poly = np.zeros((nV, mp, 2))
-        npts = np.zeros(nV, np.int32)
-        for v, t in enumerate(refs):
-            poly[v, :len(t)] = t
-            npts[v] = len(t)
-        poly = arr(poly)
-        npts = arr(npts, dtype=np.int32)
         self.u_lim = float(scenario.uLim if u_lim is None else u_lim)
         self.dt = float(scenario.dt)
-        P = LB.Params(dt=self.dt, u_lim=self.u_lim, dsafe_extra=float(scenario.dsafeExtra),
-                      constraint_tol=CONSTRAINT_TOL, delta_tol=DELTA_TOL, slack_weight=SLACK_WEIGHT,
-                      max_scp_iter=max_scp_iter, max_ipm_iter=max_ipm_iter,
-                      polish_refine=polish_refine,
-                      flags=(LB.FLAG_OBST_QUIRK if obstacle_quirk else 0) |
-                      (0 if warm_start else LB.FLAG_COLD_QP), ipm_tol=ipm_tol,
-                      polish_delta=polish_delta, polish_rho=polish_rho,
-                      lf=_dptr(lf), lr=_dptr(lr), q=_dptr(q), q_final=_dptr(qf), r=_dptr(r),
-                      dsafe_veh=_dptr(dv), dsafe_obs=_dptr(do) if nO else None,
-                      ref_polyline=_dptr(poly), ref_npts=npts.ctypes.data_as(C.POINTER(C.c_int32)),
-                      ref_max_pts=mp)
+        # the handle-level settings every variant shares (scpqp_variants.h)
+        self._knobs = dict(u_lim=u_lim, max_scp_iter=max_scp_iter, max_ipm_iter=max_ipm_iter,
+                           ipm_tol=ipm_tol, polish_delta=polish_delta, polish_rho=polish_rho,
+                           polish_refine=polish_refine, obstacle_quirk=obstacle_quirk,
+                           warm_start=warm_start)
+        P, keep = pack_params(scenario, **self._knobs)
         D = LB.Dims(n_veh=nV, hp_max=self.hp_max, n_obst=nO, max_batch=self.max_batch)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             LB.check(self.lib.scpqp_create(C.byref(D), C.byref(P), self.device.index or 0,
                                            C.byref(h)), self.lib)
         self.h = h
-        self._keep = []
+        del keep
+        self.n_variants = 1
+        if variants is not None:
+            self.set_variants(variants)
+
+    def set_variants(self, scenarios):
+        """Install the scenarios as the handle's variant table (``scpqp_set_variants``):
+        problem b of a later call uses ``scenarios[variant[b]]``.  The variants may differ
+        in Lf, Lr, Q, Q_final, R, the dsafe tables, dsafeExtra and the reference polylines;
+        the sizes, dt, uLim and the solver settings are the handle's."""
+        scenarios = list(scenarios)
+        if not scenarios:
+            raise ValueError("set_variants needs at least one scenario")
+        for k, sc in enumerate(scenarios):
+            if int(sc.nVeh) != self.nV or int(sc.nObst) != self.nO:
+                raise ValueError(f"variant {k}: nVeh / nObst differ from the solver's")
+        packed = [pack_params(sc, **self._knobs) for sc in scenarios]
+        table = (LB.Params * len(packed))(*[P for P, _ in packed])
+        with torch.cuda.device(self.device):
+            LB.check(self.lib.scpqp_set_variants(self.h, len(packed), table), self.lib)
+        del packed
+        self.n_variants = len(scenarios)
 
     def close(self):
         if getattr(self, "h", None):
@@ -142,7 +181,7 @@ class ScpQpSolver:
         return torch.as_tensor(np.ascontiguousarray(x), dtype=dtype, device=self.device)
 
     def _inputs(self, x0, u0=None, ec_noise=None, hp=None, obst=None, ref_points=None,
-                u_warm=None, max_scp_iter=0, need_obst=True):
+                u_warm=None, max_scp_iter=0, need_obst=True, variant=None):
         """Move the inputs to the device and check every size against (B, nVeh, nObst,
         hp_max) before anything is launched: the kernel indexes each per-problem slot
         with hp_max strides.  Per-problem slots are sized for hp_max; a problem of
@@ -176,10 +215,12 @@ class ScpQpSolver:
         _need(rp, B * Hm * 2 * nV, "ref_points [B, hp_max, 2, nVeh] (packed per slot)")
         uw = self._dev(u_warm)
         _need(uw, B * nV * Hm, "u_warm [B, nVeh*hp_max] (packed per slot)")
-        bufs = (x0, u0, ec, hpt, ob, rp, uw)
+        var = self._dev(variant, torch.int32)
+        _need(var, B, "variant [B]")
+        bufs = (x0, u0, ec, hpt, ob, rp, uw, var)
         bi = LB.BatchIn(x0=_vptr(x0), u0=_vptr(u0), ec_noise=_vptr(ec), hp=_vptr(hpt),
                         obst=_vptr(ob), ref_points=_vptr(rp), u_warm=_vptr(uw),
-                        max_scp_iter=int(max_scp_iter), reserved=0)
+                        max_scp_iter=int(max_scp_iter), reserved=0, variant=_vptr(var))
         return B, bi, bufs
 
     def _stream(self):
@@ -187,14 +228,17 @@ class ScpQpSolver:
 
     # ------------------------------------------------------------------ entry points
     def solve(self, x0, u0=None, ec_noise=None, hp=None, obst=None, ref_points=None, u_warm=None,
-              max_scp_iter=0, out=None, trace=False):
+              max_scp_iter=0, out=None, trace=False, variant=None):
         """SCP_controller for a batch.  Arrays: x0 [B,nVeh,6], u0 [B,nVeh], ec_noise [B,nVeh,2],
         hp [B] int, obst [B,nObst,2,hp_max], ref_points [B,hp_max,2,nVeh], u_warm
         [B,nVeh*hp_max]; per-problem slots are read as packed prefixes for hp_b < hp_max
         (see _inputs).  ``trace=True`` also records every SCP iteration (the reference's
         optimization_log, SCP_controller.py:169-189) into ``out.trace``; decode it with
-        scpqp.trace.decode."""
-        B, bi, bufs = self._inputs(x0, u0, ec_noise, hp, obst, ref_points, u_warm, max_scp_iter)
+        scpqp.trace.decode.  ``variant`` [B] int: problem b uses entry ``variant[b]`` of the
+        table of ``set_variants`` (None: entry 0); an index outside the table gives
+        ST_INVALID with zero counters, like a horizon outside its slot."""
+        B, bi, bufs = self._inputs(x0, u0, ec_noise, hp, obst, ref_points, u_warm, max_scp_iter,
+                                   variant=variant)
         if out is None:
             out = self.alloc_out(B, trace=trace)
         self._check_out(out, B)
@@ -250,8 +294,10 @@ class ScpQpSolver:
                 raise ValueError(f"output {k}: need a contiguous {want} tensor of >= {n} "
                                  f"elements on {self.device}")
 
-    def linearize(self, x0, u0=None, ec_noise=None, hp=None, obst=None, ref_points=None):
-        B, bi, bufs = self._inputs(x0, u0, ec_noise, hp, obst, ref_points, need_obst=False)
+    def linearize(self, x0, u0=None, ec_noise=None, hp=None, obst=None, ref_points=None,
+                  variant=None):
+        B, bi, bufs = self._inputs(x0, u0, ec_noise, hp, obst, ref_points, need_obst=False,
+                                   variant=variant)
         nV, Hm, dev = self.nV, self.hp_max, self.device
         f = dict(dtype=torch.float64, device=dev)
         res = dict(Ad=torch.zeros(B, nV, 6, 6, **f), Bd=torch.zeros(B, nV, 6, **f),
@@ -264,8 +310,9 @@ class ScpQpSolver:
         torch.cuda.current_stream(dev).synchronize()
         return res
 
-    def evaluate(self, u, x0, u0=None, ec_noise=None, hp=None, obst=None, ref_points=None):
-        B, bi, bufs = self._inputs(x0, u0, ec_noise, hp, obst, ref_points)
+    def evaluate(self, u, x0, u0=None, ec_noise=None, hp=None, obst=None, ref_points=None,
+                 variant=None):
+        B, bi, bufs = self._inputs(x0, u0, ec_noise, hp, obst, ref_points, variant=variant)
         nV, nO, Hm, dev = self.nV, self.nO, self.hp_max, self.device
         ut = self._dev(u).reshape(B, -1)
         if ut.shape[1] < nV * Hm:
@@ -283,8 +330,8 @@ class ScpQpSolver:
         torch.cuda.current_stream(dev).synchronize()
         return res
 
-    def sample_reference(self, x0, hp=None):
-        B, bi, bufs = self._inputs(x0, hp=hp, need_obst=False)
+    def sample_reference(self, x0, hp=None, variant=None):
+        B, bi, bufs = self._inputs(x0, hp=hp, need_obst=False, variant=variant)
         ref = torch.zeros(B, self.hp_max, 2, self.nV, dtype=torch.float64, device=self.device)
         LB.check(self.lib.scpqp_sample_reference(self.h, B, C.byref(bi),
                                                  C.c_void_p(ref.data_ptr()), self._stream()),

@@ -8,6 +8,7 @@ scipy calls + the structured SCP restatement) on a bounded sample, one
 realisation per spawned single-threaded worker.
 
     python tools/bench_rollout.py [B] [steps] [cpu_sample] [--noise-seed S] [--metrics]
+                                  [--variants K]
 
 Prints one JSON line: realisation-steps/s on the GPU and the CPU, and the
 largest state difference between the two on the CPU sample.  ``--noise-seed S``
@@ -15,6 +16,10 @@ runs the GPU rollout with the reference's model noise (include/scpqp_noise.h);
 the CPU sample stays noise-free, so the state difference then shows the noise.
 ``--metrics`` accumulates the realised-path metrics (scpqp/metrics.py) during the timed
 run and adds their batch summary: collision rate, clearance quantiles, cross-track error.
+``--variants K`` runs a ``dsafeExtra`` sweep in the one batch: K values linearly spaced
+over [0.5, 1.5], realisation b with value b mod K (include/scpqp_variants.h); it implies
+``--metrics`` and adds the summary per value.  The CPU sample runs each of its
+realisations with that realisation's value.
 """
 import json
 import multiprocessing as mp
@@ -41,8 +46,10 @@ def _cpu_worker(args):
     sys.path[:0] = [ROOT, os.path.join(ROOT, "senquential-convex-programming-for-trajectory-planning_amd")]
     from oracle import plant_reference as PR
     from oracle import scp_reference as R
-    x_init, steps, hp = args
+    x_init, steps, hp, dsafe_extra = args
     sc = R.circle_scenario(4, Hp=hp)
+    if dsafe_extra is not None:
+        sc.dsafeExtra = dsafe_extra
     cl = PR.ClosedLoop(sc, x_init=x_init)
     t0 = time.perf_counter()
     for i in range(steps):
@@ -59,9 +66,17 @@ def main():
         at = argv.index("--noise-seed")
         noise_seed = int(argv[at + 1], 0)
         del argv[at:at + 2]
+    n_var = 0
+    if "--variants" in argv:
+        at = argv.index("--variants")
+        n_var = int(argv[at + 1])
+        del argv[at:at + 2]
+        if n_var < 1:
+            raise SystemExit("--variants K needs K >= 1")
     metrics = "--metrics" in argv
     if metrics:
         argv.remove("--metrics")
+    metrics = metrics or n_var > 0
     B = int(argv[0]) if len(argv) > 0 else 1024
     steps = int(argv[1]) if len(argv) > 1 else 5
     cpu_n = int(argv[2]) if len(argv) > 2 else 16
@@ -70,14 +85,26 @@ def main():
     sc = R.circle_scenario(4, Hp=hp)
     x_init = initial_states(sc, B)
     cpu_n = min(cpu_n, B)
+    variants = variant_of = None
+    extras = [None] * B
+    if n_var:
+        values = np.linspace(0.5, 1.5, n_var)
+        variants = []
+        for v in values:
+            sk = R.circle_scenario(4, Hp=hp)
+            sk.dsafeExtra = float(v)
+            variants.append(sk)
+        variant_of = np.arange(B) % n_var
+        extras = [float(values[k]) for k in variant_of]
     t0 = time.perf_counter()
     with mp.get_context("spawn").Pool(cpu_n) as pool:
-        cpu = pool.map(_cpu_worker, [(x_init[b], steps, hp) for b in range(cpu_n)])
+        cpu = pool.map(_cpu_worker, [(x_init[b], steps, hp, extras[b]) for b in range(cpu_n)])
     cpu_wall = time.perf_counter() - t0
 
     import torch
     from scpqp.rollout import ClosedLoopBatch
-    cl = ClosedLoopBatch(sc, B, device="cuda", metrics=metrics)
+    cl = ClosedLoopBatch(sc, B, device="cuda", metrics=metrics, variants=variants,
+                         variant_of=variant_of)
     cl.reset(x_init, seed=noise_seed)
     cl.run(1)                      # warm-up (library load, first launches)
     torch.cuda.synchronize()
@@ -104,6 +131,10 @@ def main():
     }
     if metrics:
         out["metrics"] = summary
+    if n_var:
+        from scpqp.metrics import summarize_by_variant
+        by = summarize_by_variant(cl.metrics(), variant_of)
+        out["variants"] = [{"dsafe_extra": float(values[k]), "metrics": by[k]} for k in sorted(by)]
     print(json.dumps(out))
     cl.close()
 

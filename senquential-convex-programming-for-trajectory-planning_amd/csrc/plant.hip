@@ -11,6 +11,10 @@
 //                           the same integrators with the reference's model noise
 //                           drawn anew per right-hand-side evaluation
 //                           (include/scpqp_noise.h, Model.py:84-86)
+//   scpqp_plant_step_truth, scpqp_truth_fill_nominal, scpqp_truth_sample
+//                           the plant step with per-(realisation, vehicle) plant
+//                           parameters the controller does not know, and their
+//                           sampler (include/scpqp_truth.h)
 //
 // The reference integrates with scipy (odeint = LSODA at rtol = atol = 1.49e-8
 // for the delay compensation, dopri5 at rtol = atol = 1e-8 for the plant).
@@ -24,9 +28,11 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
+#include <stdio.h>
 
 #include "scpqp_noise.h"
 #include "scpqp_philox.h"
+#include "scpqp_truth.h"
 
 int scpqp_fail_(int code, const char* msg);   // scpqp.hip: sets scpqp_last_error()
 
@@ -59,12 +65,40 @@ __device__ __forceinline__ void bicycle(const double (&x)[NX], const Veh& p, dou
     dx[5] = (p.uref - x[5]) / 0.1;
 }
 
+// a * b + c in two roundings, the __dadd_rn(__dmul_rn(a, b), c) of include/scpqp_truth.h.
+// Spelled with the operators under contract(off): the two intrinsics are plain * and +
+// to the compiler, which would fuse them into one fma (one rounding) once inlined.
+__device__ __forceinline__ double mul_add_2r(double a, double b, double c) {
+#pragma clang fp contract(off)
+    const double ab = a * b;
+    return ab + c;
+}
+
+// a vehicle of the plant truth (include/scpqp_truth.h): uref holds u_eff, formed once
+// per lane, and tau divides where 0.1 does; the right-hand side is otherwise bicycle()'s
+struct VehT : Veh {
+    double tau;
+};
+
+__device__ __forceinline__ void bicycle(const double (&x)[NX], const VehT& p, double (&dx)[NX]) {
+    const double L = p.lf + p.lr, R = p.lr / L;
+    const double tu = tan(x[5]);
+    const double vc = x[3] * sqrt(1.0 + (R * tu) * (R * tu));
+    const double beta = atan(R * tu);
+    dx[0] = vc * cos(x[2] + beta) + p.n0;
+    dx[1] = vc * sin(x[2] + beta) + p.n1;
+    dx[2] = vc * tu * cos(beta) / L;
+    dx[3] = x[4];
+    dx[4] = 0.0;
+    dx[5] = (p.uref - x[5]) / p.tau;
+}
+
 using scpqp_noise_dev::Stream;
 
 // kNoisy: p.n0, p.n1 are redrawn before each of the four evaluations (c0 order
 // k1, k2, k3, k4); else p is left as it is and ns is unused
-template <bool kNoisy>
-__device__ __forceinline__ void rk4(double (&x)[NX], Veh& p, double h, Stream& ns) {
+template <bool kNoisy, class VehX>
+__device__ __forceinline__ void rk4(double (&x)[NX], VehX& p, double h, Stream& ns) {
     double k1[NX], k2[NX], k3[NX], k4[NX], y[NX];
     if constexpr (kNoisy) scpqp_noise_dev::draw(ns, p.n0, p.n1);
     bicycle(x, p, k1);
@@ -85,8 +119,8 @@ __device__ __forceinline__ void rk4(double (&x)[NX], Veh& p, double h, Stream& n
 }
 
 // integrate x over a span of length T with n equal RK4 steps
-template <bool kNoisy>
-__device__ __forceinline__ void flow(double (&x)[NX], Veh& p, double T, int n, Stream& ns) {
+template <bool kNoisy, class VehX>
+__device__ __forceinline__ void flow(double (&x)[NX], VehX& p, double T, int n, Stream& ns) {
     const double h = T / n;
     for (int s = 0; s < n; ++s) rk4<kNoisy>(x, p, h, ns);
 }
@@ -192,6 +226,105 @@ __global__ __launch_bounds__(PT) void plant_kernel_noisy(scpqp_plant_params p, i
     plant_lane<true>(p, B, n_ticks, tick, hmax, x_start, u_tick, nullptr, nz, x_path);
 }
 
+// plant_lane with the lane's truth row (include/scpqp_truth.h): five loads, the
+// validity guard, u_eff, then the same integration with the same step count.  A bad
+// row makes its own outputs NaN and integrates nothing.
+template <bool kNoisy>
+__device__ __forceinline__ void plant_lane_truth(int V, int B, int n_ticks, double tick,
+                                                 double hmax, const double* x_start,
+                                                 const double* u_tick, const double* truth,
+                                                 const double* noise, const scpqp_noise& nz,
+                                                 double* x_path) {
+    const int K = n_ticks + 1;
+    const int g = blockIdx.x * PT + threadIdx.x;
+    if (g >= B * V * K) return;
+    const int k = g % K, bv = g / K, v = bv % V;
+    const double* row = truth + (size_t)bv * SCPQP_TRUTH_NP;
+    const double lf = row[SCPQP_TRUTH_LF], lr = row[SCPQP_TRUTH_LR], tau = row[SCPQP_TRUTH_TAU];
+    const double gain = row[SCPQP_TRUTH_GAIN], bias = row[SCPQP_TRUTH_BIAS];
+    if (!(lf + lr > 0.0) || !(tau > 0.0)) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) x_path[(size_t)g * NX + i] = __builtin_nan("");
+        return;
+    }
+    VehT q{{lf, lr, mul_add_2r(gain, u_tick[g], bias), noise ? noise[2 * bv] : 0.0,
+            noise ? noise[2 * bv + 1] : 0.0},
+           tau};
+    Stream ns{};
+    if constexpr (kNoisy)
+        ns = scpqp_noise_dev::make_stream(nz.seed, nz.sigma, nz.epoch, SCPQP_NOISE_SITE_PLANT,
+                                          (uint32_t)k, (uint32_t)v, nz.b_offset + (uint32_t)(bv / V));
+    double x[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) x[i] = x_start[(size_t)bv * NX + i];
+    if (k > 0) {
+        const double T = k * tick;
+        flow<kNoisy>(x, q, T, steps_for(T, hmax), ns);
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i) x_path[(size_t)g * NX + i] = x[i];
+}
+
+__global__ __launch_bounds__(PT) void plant_kernel_truth(int V, int B, int n_ticks, double tick,
+                                                         double hmax, const double* x_start,
+                                                         const double* u_tick,
+                                                         const double* truth,
+                                                         const double* noise, double* x_path) {
+    plant_lane_truth<false>(V, B, n_ticks, tick, hmax, x_start, u_tick, truth, noise,
+                            scpqp_noise{}, x_path);
+}
+
+__global__ __launch_bounds__(PT) void plant_kernel_truth_noisy(int V, int B, int n_ticks,
+                                                               double tick, double hmax,
+                                                               const double* x_start,
+                                                               const double* u_tick,
+                                                               const double* truth, scpqp_noise nz,
+                                                               double* x_path) {
+    plant_lane_truth<true>(V, B, n_ticks, tick, hmax, x_start, u_tick, truth, nullptr, nz,
+                           x_path);
+}
+
+// one lane per (problem, vehicle): the nominal row of include/scpqp_truth.h
+__global__ __launch_bounds__(PT) void truth_nominal_kernel(scpqp_plant_params p, int B,
+                                                           double* truth) {
+    const int g = blockIdx.x * PT + threadIdx.x;
+    if (g >= B * p.n_veh) return;
+    const int v = g % p.n_veh;
+    double* row = truth + (size_t)g * SCPQP_TRUTH_NP;
+    row[SCPQP_TRUTH_LF] = p.lf[v];
+    row[SCPQP_TRUTH_LR] = p.lr[v];
+    row[SCPQP_TRUTH_TAU] = SCPQP_TRUTH_TAU_NOMINAL;
+    row[SCPQP_TRUTH_GAIN] = 1.0;
+    row[SCPQP_TRUTH_BIAS] = 0.0;
+}
+
+// one lane per (problem, vehicle): field f from the one Philox call of counter
+// (f, 0, (site 3 << 24) | v, b_offset + b)
+__global__ __launch_bounds__(PT) void truth_sample_kernel(scpqp_truth_dist d, int B,
+                                                          double* truth) {
+    const int g = blockIdx.x * PT + threadIdx.x;
+    if (g >= B * d.n_veh) return;
+    const int b = g / d.n_veh, v = g % d.n_veh;
+    double* row = truth + (size_t)g * SCPQP_TRUTH_NP;
+    for (int f = 0; f < SCPQP_TRUTH_NP; ++f) {
+        const scpqp_truth_field& fd = d.field[f];
+        const double mean = d.mean[f][v];
+        if (fd.kind == SCPQP_TRUTH_FIXED) {
+            row[f] = mean;
+            continue;
+        }
+        uint32_t c[4] = {(uint32_t)f, 0u, ((uint32_t)SCPQP_NOISE_SITE_TRUTH << 24) | (uint32_t)v,
+                         d.b_offset + (uint32_t)b};
+        scpqp_noise_dev::philox4x32_10(c, (uint32_t)d.seed, (uint32_t)(d.seed >> 32));
+        double u1, u2;
+        scpqp_noise_dev::uniforms(c, u1, u2);
+        const double xi = fd.kind == SCPQP_TRUTH_UNIFORM
+                              ? 2.0 * u2 - 1.0
+                              : sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+        row[f] = fmin(fmax(mul_add_2r(fd.spread, xi, mean), fd.lo), fd.hi);
+    }
+}
+
 // one lane per (problem, vehicle): the first n_eval draws of the (site, k) stream
 __global__ __launch_bounds__(PT) void fill_kernel(scpqp_noise nz, int B, int V, int site, int k,
                                                   int n_eval, double* out) {
@@ -238,6 +371,39 @@ int check_noise(const scpqp_noise* nz) {
     if (!nz) return scpqp_fail_(SCPQP_E_ARG, "null noise parameters");
     if (!(nz->sigma >= 0.0) || isinf(nz->sigma))
         return scpqp_fail_(SCPQP_E_ARG, "sigma must be finite and >= 0");
+    return 0;
+}
+
+const char* const TRUTH_FIELD[SCPQP_TRUTH_NP] = {"lf", "lr", "tau", "gain", "bias"};
+
+int fail_field(const char* what, int f) {
+    static thread_local char msg[96];
+    snprintf(msg, sizeof msg, "truth field %s: %s", TRUTH_FIELD[f], what);
+    return scpqp_fail_(SCPQP_E_ARG, msg);
+}
+
+int check_truth_dist(const scpqp_truth_dist* d) {
+    if (!d) return scpqp_fail_(SCPQP_E_ARG, "null truth distribution");
+    if (d->n_veh < 1 || d->n_veh > SCPQP_MAX_VEH) return scpqp_fail_(SCPQP_E_ARG, "n_veh out of range");
+    for (int f = 0; f < SCPQP_TRUTH_NP; ++f) {
+        const scpqp_truth_field& fd = d->field[f];
+        if (fd.kind < SCPQP_TRUTH_FIXED || fd.kind > SCPQP_TRUTH_NORMAL)
+            return fail_field("kind must be 0 (fixed), 1 (uniform) or 2 (normal)", f);
+        if (fd.kind == SCPQP_TRUTH_FIXED) continue;
+        if (!(fd.spread >= 0.0) || isinf(fd.spread))
+            return fail_field("spread must be finite and >= 0", f);
+        if (!(fd.lo <= fd.hi)) return fail_field("lo must be <= hi", f);
+    }
+    // the smallest value the sampler can emit: never a row the plant would NaN
+    auto floor_of = [d](int f, int v) {
+        return d->field[f].kind == SCPQP_TRUTH_FIXED ? d->mean[f][v] : d->field[f].lo;
+    };
+    for (int v = 0; v < d->n_veh; ++v) {
+        if (!(floor_of(SCPQP_TRUTH_LF, v) + floor_of(SCPQP_TRUTH_LR, v) > 0.0))
+            return fail_field("the smallest lf + lr must be > 0", SCPQP_TRUTH_LF);
+        if (!(floor_of(SCPQP_TRUTH_TAU, v) > 0.0))
+            return fail_field("the smallest tau must be > 0", SCPQP_TRUTH_TAU);
+    }
     return 0;
 }
 
@@ -337,6 +503,61 @@ int scpqp_noise_fill(const scpqp_noise* nz, int32_t B, int32_t n_veh, int32_t si
     if (!out) return scpqp_fail_(SCPQP_E_ARG, "null array");
     hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((n + PT - 1) / PT)), dim3(PT), 0,
                        static_cast<hipStream_t>(stream), *nz, B, n_veh, site, k, n_eval, out);
+    return launched();
+}
+
+int scpqp_plant_step_truth(const scpqp_plant_params* p, int32_t B, int32_t n_ticks, double tick,
+                           const double* x_start, const double* u_tick, const double* truth,
+                           const double* noise, const scpqp_noise* nz,
+                           double* x_path, double h_max, void* stream) {
+    if (!p) return scpqp_fail_(SCPQP_E_ARG, "null plant params");
+    if (p->n_veh < 1 || p->n_veh > SCPQP_MAX_VEH) return scpqp_fail_(SCPQP_E_ARG, "n_veh out of range");
+    if (noise && nz)
+        return scpqp_fail_(SCPQP_E_ARG, "pass either noise (constant terms) or nz, not both");
+    if (nz)
+        if (int rc = check_noise(nz)) return rc;
+    if (B < 0 || n_ticks < 0) return scpqp_fail_(SCPQP_E_ARG, "batch size / n_ticks < 0");
+    if (nz && n_ticks >= SCPQP_NOISE_MAX_TICKS)
+        return scpqp_fail_(SCPQP_E_SIZE, "n_ticks must be < 65536 (16 bits of the counter)");
+    if (!(tick > 0.0) || !(h_max > 0.0)) return scpqp_fail_(SCPQP_E_ARG, "bad tick / h_max");
+    if (B == 0) return 0;
+    if (!truth) return scpqp_fail_(SCPQP_E_ARG, "null truth array");
+    if (!x_start || !u_tick || !x_path) return scpqp_fail_(SCPQP_E_ARG, "null array");
+    const long long n = (long long)B * p->n_veh * (n_ticks + 1);
+    if (n > 0x7fffffffLL) return scpqp_fail_(SCPQP_E_SIZE, "B * n_veh * (n_ticks + 1) too large");
+    const dim3 grid((unsigned)((n + PT - 1) / PT));
+    if (nz)
+        hipLaunchKernelGGL(plant_kernel_truth_noisy, grid, dim3(PT), 0,
+                           static_cast<hipStream_t>(stream), (int)p->n_veh, B, n_ticks, tick,
+                           h_max, x_start, u_tick, truth, *nz, x_path);
+    else
+        hipLaunchKernelGGL(plant_kernel_truth, grid, dim3(PT), 0,
+                           static_cast<hipStream_t>(stream), (int)p->n_veh, B, n_ticks, tick,
+                           h_max, x_start, u_tick, truth, noise, x_path);
+    return launched();
+}
+
+int scpqp_truth_fill_nominal(const scpqp_plant_params* p, int32_t B, double* truth, void* stream) {
+    if (int rc = check_params(p)) return rc;
+    if (B < 0) return scpqp_fail_(SCPQP_E_ARG, "batch size < 0");
+    if (B == 0) return 0;
+    if (!truth) return scpqp_fail_(SCPQP_E_ARG, "null truth array");
+    const long long n = (long long)B * p->n_veh;
+    if (n * SCPQP_TRUTH_NP > 0x7fffffffLL) return scpqp_fail_(SCPQP_E_SIZE, "B * n_veh too large");
+    hipLaunchKernelGGL(truth_nominal_kernel, dim3((unsigned)((n + PT - 1) / PT)), dim3(PT), 0,
+                       static_cast<hipStream_t>(stream), *p, B, truth);
+    return launched();
+}
+
+int scpqp_truth_sample(const scpqp_truth_dist* d, int32_t B, double* truth, void* stream) {
+    if (int rc = check_truth_dist(d)) return rc;
+    if (B < 0) return scpqp_fail_(SCPQP_E_ARG, "batch size < 0");
+    if (B == 0) return 0;
+    if (!truth) return scpqp_fail_(SCPQP_E_ARG, "null truth array");
+    const long long n = (long long)B * d->n_veh;
+    if (n * SCPQP_TRUTH_NP > 0x7fffffffLL) return scpqp_fail_(SCPQP_E_SIZE, "B * n_veh too large");
+    hipLaunchKernelGGL(truth_sample_kernel, dim3((unsigned)((n + PT - 1) / PT)), dim3(PT), 0,
+                       static_cast<hipStream_t>(stream), *d, B, truth);
     return launched();
 }
 

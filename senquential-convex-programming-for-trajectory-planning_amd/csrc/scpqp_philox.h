@@ -29,6 +29,15 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
     }
 }
 
+// the raw uniforms of one call's four words (include/scpqp_noise.h): u1 in (0, 1],
+// u2 in [0, 1)
+__device__ __forceinline__ void uniforms(const uint32_t (&c)[4], double& u1, double& u2) {
+    const uint64_t a = (((uint64_t)c[0] << 32) | c[1]) >> 11;
+    const uint64_t b = (((uint64_t)c[2] << 32) | c[3]) >> 11;
+    u1 = (double)(a + 1) * 0x1p-53;
+    u2 = (double)b * 0x1p-53;
+}
+
 // the stream of one lane: key, (c1, c2, c3) and the running evaluation index c0
 struct Stream {
     uint32_t k0, k1, c0, c1, c2, c3;

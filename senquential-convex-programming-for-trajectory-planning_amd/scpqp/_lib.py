@@ -1,5 +1,6 @@
 """ctypes binding of ``include/scpqp.h``, ``include/scpqp_noise.h``,
-``include/scpqp_metrics.h`` and ``include/scpqp_variants.h`` (the C-ABI of the HIP library).
+``include/scpqp_metrics.h``, ``include/scpqp_variants.h`` and ``include/scpqp_truth.h``
+(the C-ABI of the HIP library).
 
 The shared library ``libscpqp.so`` is built in-tree (``__graft_entry__.build()``
 or ``python -m scpqp.build``).  There is no CPU fallback: if the library or a
@@ -129,6 +130,30 @@ METRICS_EXPORTS = ("scpqp_metrics_create", "scpqp_metrics_destroy", "scpqp_metri
 VARIANT_EXPORTS = ("scpqp_set_variants", "scpqp_metrics_set_variants",
                    "scpqp_metrics_accumulate_variants")
 
+TRUTH_NP = 5
+TRUTH_LF, TRUTH_LR, TRUTH_TAU, TRUTH_GAIN, TRUTH_BIAS = range(TRUTH_NP)
+TRUTH_FIELDS = ("lf", "lr", "tau", "gain", "bias")
+TRUTH_TAU_NOMINAL = 0.1
+TRUTH_FIXED, TRUTH_UNIFORM, TRUTH_NORMAL = 0, 1, 2
+NOISE_SITE_TRUTH = 3
+
+
+class TruthField(C.Structure):
+    """scpqp_truth_field (include/scpqp_truth.h)."""
+    _fields_ = [("kind", C.c_int32), ("pad0", C.c_int32), ("spread", C.c_double),
+                ("lo", C.c_double), ("hi", C.c_double)]
+
+
+class TruthDist(C.Structure):
+    """scpqp_truth_dist (include/scpqp_truth.h)."""
+    _fields_ = [("n_veh", C.c_int32), ("pad0", C.c_int32),
+                ("mean", (C.c_double * MAX_VEH) * TRUTH_NP), ("field", TruthField * TRUTH_NP),
+                ("seed", C.c_uint64), ("b_offset", C.c_uint32), ("pad1", C.c_uint32)]
+
+
+# every symbol include/scpqp_truth.h declares (checked by tests/test_truth_host.py)
+TRUTH_EXPORTS = ("scpqp_plant_step_truth", "scpqp_truth_fill_nominal", "scpqp_truth_sample")
+
 _lib = None
 
 
@@ -205,6 +230,15 @@ def load(path=None):
         lib.scpqp_metrics_accumulate_variants.argtypes = [H, C.c_int32, C.c_int32, C.c_int32,
                                                           C.c_int32, V, MA, MD, V, V]
         lib.scpqp_metrics_accumulate_variants.restype = C.c_int
+    # likewise an A/B build from before the plant truth
+    if path is None or hasattr(lib, "scpqp_plant_step_truth"):
+        lib.scpqp_plant_step_truth.argtypes = [PP, C.c_int32, C.c_int32, C.c_double, V, V, V, V, NP,
+                                               V, C.c_double, V]
+        lib.scpqp_plant_step_truth.restype = C.c_int
+        lib.scpqp_truth_fill_nominal.argtypes = [PP, C.c_int32, V, V]
+        lib.scpqp_truth_fill_nominal.restype = C.c_int
+        lib.scpqp_truth_sample.argtypes = [C.POINTER(TruthDist), C.c_int32, V, V]
+        lib.scpqp_truth_sample.restype = C.c_int
     if path is None:
         _lib = lib
     return lib

@@ -49,7 +49,8 @@ def build_library(force=False, verbose=False, defines=(), out=None, csrc=None):
     deps = srcs + [ksrc, hdr, os.path.join(src_dir, "scpqp_philox.h"),
                    os.path.join(INCLUDE, "scpqp.h"), os.path.join(INCLUDE, "scpqp_noise.h"),
                    os.path.join(INCLUDE, "scpqp_metrics.h"),
-                   os.path.join(INCLUDE, "scpqp_variants.h"), __file__]
+                   os.path.join(INCLUDE, "scpqp_variants.h"),
+                   os.path.join(INCLUDE, "scpqp_truth.h"), __file__]
     if not force and os.path.exists(out):
         t = os.path.getmtime(out)
         if all(os.path.getmtime(d) <= t for d in deps):

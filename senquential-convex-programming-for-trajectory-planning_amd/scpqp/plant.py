@@ -7,6 +7,8 @@
                       (Model.py:84-86), drawn on the device per right-hand-side
                       evaluation (include/scpqp_noise.h); ``rng=`` of the two
                       integrators, and ``draw_ec_noise`` for the solve's ec_noise
+``plant_step(..., truth=)``  the plant step with a truth row per (realisation, vehicle)
+                      (include/scpqp_truth.h; rows from scpqp/truth.py)
 
 Arrays are torch-ROCm float64 tensors on the GPU; PyTorch only provides the
 memory and the stream.  The reference integrates with scipy (odeint / dopri5);
@@ -118,12 +120,16 @@ def delay_compensate(params, x_meas, u_hold, horizon, n_out=DELAY_STEPS, noise=N
     return x0, traj
 
 
-def plant_step(params, x_start, u_tick, tick, noise=None, h_max=H_MAX, device=None, rng=None):
+def plant_step(params, x_start, u_tick, tick, noise=None, h_max=H_MAX, device=None, rng=None,
+               truth=None):
     """x_start [B, nVeh, 6], u_tick [B, nVeh, K] (K = ticks_per_sim + 1) ->
     x_path [B, nVeh, K, 6]: main.py:184-191 (output k integrated from t0 over
     k ticks with the constant control u_tick[..., k]).  ``noise`` / ``rng`` as in
     delay_compensate; with ``rng`` every output tick k has its own noise stream, as
-    every restart of the reference's integrator consumes fresh draws."""
+    every restart of the reference's integrator consumes fresh draws.  ``truth``
+    [B, nVeh, 5]: the plant parameters of every (realisation, vehicle)
+    (include/scpqp_truth.h; scpqp/truth.py) instead of ``params``' geometry and the
+    nominal steering lag.  delay_compensate takes none: it is the controller's prediction."""
     _one_noise_source(noise, rng)
     device = torch.device(device or "cuda")
     lib = LB.load()
@@ -135,6 +141,18 @@ def plant_step(params, x_start, u_tick, tick, noise=None, h_max=H_MAX, device=No
         raise ValueError("x_start must be [B, nVeh, 6] and u_tick [B, nVeh, K]")
     nz = None if noise is None else _dev(noise, device)
     out = torch.empty((B, V, K, 6), dtype=torch.float64, device=device)
+    if truth is not None:
+        tr = _dev(truth, device)
+        if tuple(tr.shape) != (B, V, LB.TRUTH_NP):
+            raise ValueError("truth must be [B, nVeh, 5]")
+        if nz is not None and tuple(nz.shape) != (B, V, 2):
+            raise ValueError("noise must be [B, nVeh, 2]")
+        ns = None if rng is None else rng.c_struct()
+        LB.check(lib.scpqp_plant_step_truth(C.byref(params), B, K - 1, float(tick), _ptr(x),
+                                            _ptr(u), _ptr(tr), _ptr(nz),
+                                            None if ns is None else C.byref(ns), _ptr(out),
+                                            float(h_max), _stream(device)), lib)
+        return out
     if rng is not None:
         ns = rng.c_struct()
         LB.check(lib.scpqp_plant_step_noisy(C.byref(params), B, K - 1, float(tick), _ptr(x),

@@ -24,7 +24,9 @@ initial state and, with ``reset(..., seed=)``, by the reference's model noise
 (Model.py:84-86): drawn on the device per right-hand-side evaluation from a
 counter-based generator (include/scpqp_noise.h), reproducible from the seed and
 independent of how the realisations are sharded.  ``noise=`` instead holds a
-caller-made constant pair per vehicle over the whole rollout.
+caller-made constant pair per vehicle over the whole rollout.  ``reset(..., truth=)``
+gives the plant of every (realisation, vehicle) its own geometry, steering lag, gain and
+offset (include/scpqp_truth.h), unknown to the controller.
 """
 from __future__ import annotations
 
@@ -186,7 +188,7 @@ class ClosedLoopBatch:
             from .metrics import PathMetrics
             self.path_metrics = PathMetrics(scenario, self.B, self.device, variants=self.variants)
 
-    def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0):
+    def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0, truth=None):
         """main.py:73-75: vehiclePathFullRes[:, v, 0] = x0; the control path holds
         scenario.u0 for the first ticks_delay_u + ticks_per_sim + 1 ticks.
 
@@ -194,7 +196,20 @@ class ClosedLoopBatch:
         Model.py:84-86), drawn on the device per right-hand-side evaluation: step i uses
         epoch i for its delay compensation, its plant step and the ec_noise of its solve.
         Realisation b draws as global realisation ``b_offset + b``, so a batch sharded
-        over ranks (b_offset = rank * per_rank) computes what one large batch would."""
+        over ranks (b_offset = rank * per_rank) computes what one large batch would.
+
+        ``truth`` [B, nVeh, 5] (scpqp/truth.py; include/scpqp_truth.h): the plant that
+        realises the path has these parameters per (realisation, vehicle).  Only the plant
+        step reads them: the delay compensation, the solve, the steering limit and the
+        evaluation keep the scenario's nominal model (main.py:121-123).  Validated here,
+        before anything is launched; None: nothing is allocated and the nominal kernels run."""
+        if truth is not None:
+            from . import truth as TR
+            t = truth.detach().cpu().numpy() if isinstance(truth, torch.Tensor) \
+                else np.asarray(truth, float)
+            if tuple(t.shape) != (self.B, self.nV, TR.NP):
+                raise ValueError("truth must be [B, nVeh, 5]")
+            TR.validate(t, self.h_max)
         if seed is None and getattr(getattr(self.sc, "model", None), "is_noise", False):
             raise ValueError("scenario.model.is_noise is set: pass reset(..., seed=...) to run "
                              "the rollout with model noise (it never runs noise-free silently)")
@@ -212,6 +227,8 @@ class ClosedLoopBatch:
         self.control[:, :, 0:self.tdu + self.tps + 1] = u0[None, :, None]
         self.noise = None if noise is None else torch.as_tensor(noise, dtype=torch.float64,
                                                                 device=self.device)
+        self.truth = None if truth is None else torch.as_tensor(
+            truth, dtype=torch.float64, device=self.device).contiguous()
         self.last_path = None
         self.u_prev = None
         self.history = []
@@ -297,7 +314,7 @@ class ClosedLoopBatch:
         idx = [min(self.ticks_total, math.ceil(t / sc.tick_length) + 1) for t in timelist]
         u_tick = self.control[:, :, torch.as_tensor(idx, device=self.device)].contiguous()
         path = PL.plant_step(self.params, self.state, u_tick, sc.tick_length, noise=self.noise,
-                             h_max=self.h_max, device=self.device, rng=rng)
+                             h_max=self.h_max, device=self.device, rng=rng, truth=self.truth)
         if self.path_metrics is not None:
             # every global tick once: entry 0 of a later step is the previous step's last
             self.path_metrics.accumulate(path, tick0=i * tps, k_first=0 if i == 0 else 1,

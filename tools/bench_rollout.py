@@ -8,7 +8,7 @@ scipy calls + the structured SCP restatement) on a bounded sample, one
 realisation per spawned single-threaded worker.
 
     python tools/bench_rollout.py [B] [steps] [cpu_sample] [--noise-seed S] [--metrics]
-                                  [--variants K]
+                                  [--variants K] [--mismatch PCT [--truth-seed S]]
 
 Prints one JSON line: realisation-steps/s on the GPU and the CPU, and the
 largest state difference between the two on the CPU sample.  ``--noise-seed S``
@@ -20,6 +20,13 @@ run and adds their batch summary: collision rate, clearance quantiles, cross-tra
 over [0.5, 1.5], realisation b with value b mod K (include/scpqp_variants.h); it implies
 ``--metrics`` and adds the summary per value.  The CPU sample runs each of its
 realisations with that realisation's value.
+``--mismatch PCT`` runs the timed batch with a plant truth (include/scpqp_truth.h):
+``TruthDist.relative(PCT)``, i.e. lf, lr, the steering lag and the steering gain of every
+(realisation, vehicle) uniform within +-PCT % of nominal, drawn on the device from
+``--truth-seed`` (default 1); the controller keeps the nominal model.  It implies
+``--metrics`` and prints the summary beside that of the same batch with the nominal plant
+(``metrics_nominal``, an untimed second run); with ``--variants K`` both per value.  The CPU
+sample stays nominal, so the state difference then shows the mismatch.
 """
 import json
 import multiprocessing as mp
@@ -73,10 +80,21 @@ def main():
         del argv[at:at + 2]
         if n_var < 1:
             raise SystemExit("--variants K needs K >= 1")
+    mismatch, truth_seed = None, 1
+    if "--mismatch" in argv:
+        at = argv.index("--mismatch")
+        mismatch = float(argv[at + 1])
+        del argv[at:at + 2]
+    if "--truth-seed" in argv:
+        at = argv.index("--truth-seed")
+        truth_seed = int(argv[at + 1], 0)
+        del argv[at:at + 2]
+        if mismatch is None:
+            raise SystemExit("--truth-seed needs --mismatch PCT")
     metrics = "--metrics" in argv
     if metrics:
         argv.remove("--metrics")
-    metrics = metrics or n_var > 0
+    metrics = metrics or n_var > 0 or mismatch is not None
     B = int(argv[0]) if len(argv) > 0 else 1024
     steps = int(argv[1]) if len(argv) > 1 else 5
     cpu_n = int(argv[2]) if len(argv) > 2 else 16
@@ -105,10 +123,14 @@ def main():
     from scpqp.rollout import ClosedLoopBatch
     cl = ClosedLoopBatch(sc, B, device="cuda", metrics=metrics, variants=variants,
                          variant_of=variant_of)
-    cl.reset(x_init, seed=noise_seed)
+    truth = None
+    if mismatch is not None:
+        from scpqp.truth import TruthDist
+        truth = TruthDist(sc, truth_seed).relative(mismatch).sample(B, device="cuda")
+    cl.reset(x_init, seed=noise_seed, truth=truth)
     cl.run(1)                      # warm-up (library load, first launches)
     torch.cuda.synchronize()
-    cl.reset(x_init, seed=noise_seed)
+    cl.reset(x_init, seed=noise_seed, truth=truth)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     hist = cl.run(steps)
@@ -135,6 +157,16 @@ def main():
         from scpqp.metrics import summarize_by_variant
         by = summarize_by_variant(cl.metrics(), variant_of)
         out["variants"] = [{"dsafe_extra": float(values[k]), "metrics": by[k]} for k in sorted(by)]
+    if mismatch is not None:
+        # the same batch with the nominal plant, untimed: what the mismatch costs
+        out["mismatch_pct"], out["truth_seed"] = mismatch, truth_seed
+        cl.reset(x_init, seed=noise_seed)
+        cl.run(steps)
+        out["metrics_nominal"] = cl.metrics_summary()
+        if n_var:
+            by = summarize_by_variant(cl.metrics(), variant_of)
+            for row, k in zip(out["variants"], sorted(by)):
+                row["metrics_nominal"] = by[k]
     print(json.dumps(out))
     cl.close()
 

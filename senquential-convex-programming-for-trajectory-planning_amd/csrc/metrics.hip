@@ -21,6 +21,17 @@
 // Steps 1-3 run per chunk of ticks (ENT_CAP staged entries: the whole step for up
 // to 16 vehicles x 42 ticks); lane state carries over the chunks, so the chunking
 // does not show in any result.
+//
+// scpqp_metrics_accumulate_obstacles (include/scpqp_obstacles.h) runs the same kernel
+// instantiated with kRows: obstacle o of realisation b is posed by its own row at the
+// tick's time, per (tick, vehicle, obstacle) item and in registers.  The constant
+// obstacles' once-per-workgroup cos / sin staging cannot serve a pose that depends on the
+// tick, and staging [ticks][n_obst] poses would bound the chunk by ticks x n_obst as well
+// (frog's 22 obstacles: 30 ticks, its 41-entry step cut in two) for 21 KB more LDS.  The
+// per-item pose repeats a row's sincos n_veh times per tick; the scenarios with obstacles
+// have 1 and 5 vehicles, and the chunking stays that of the constant obstacles, so the
+// nominal rows give bitwise what those give.  The instantiation without kRows is the
+// kernel the other entry points have always launched.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -28,6 +39,8 @@
 #include <vector>
 
 #include "scpqp_metrics.h"
+#include "scpqp_obstacle_pose.h"
+#include "scpqp_obstacles.h"
 #include "scpqp_variants.h"
 
 int scpqp_fail_(int code, const char* msg);   // scpqp.hip: sets scpqp_last_error()
@@ -131,12 +144,16 @@ __device__ __forceinline__ double wave_min(double x) {
     return x;
 }
 
+// kRows: obstacle o of realisation b is rows[b][o] (include/scpqp_obstacles.h) instead of
+// the constants' P->obst[o]; rows is not read otherwise
+template <bool kRows>
 __global__ __launch_bounds__(WAVE) void metrics_kernel(const DevConst* __restrict__ table, int n_var,
                                                        const int* __restrict__ variant, int n_ticks,
                                                        int tick0, int k_first,
                                                        const double* __restrict__ x_path,
                                                        scpqp_metrics_acc acc, bool have_acc,
-                                                       scpqp_metrics_dense dense) {
+                                                       scpqp_metrics_dense dense,
+                                                       const double* __restrict__ rows) {
     __shared__ double pose[ENT_CAP][4];     // x, y, cos h, sin h of entry (tick, vehicle)
     __shared__ double xt[ENT_CAP];          // its cross-track error
     __shared__ int coll[ENT_CAP];           // per tick of the chunk: any gap of 0
@@ -153,8 +170,18 @@ __global__ __launch_bounds__(WAVE) void metrics_kernel(const DevConst* __restric
     const int nVO = nV * nO;
     const int chunk = ENT_CAP / nV;         // ticks per chunk (>= 42)
     const double* xb = x_path + b * nV * K * NX;
+    const double* rb = nullptr;             // kRows: the realisation's rows [nO][7]
 
-    for (int o = lane; o < nO; o += WAVE) sincos(P->obst[o][2], &ocs[o][1], &ocs[o][0]);
+    if constexpr (kRows) {
+        // a bad row leaves the realisation untouched, like a bad variant index: the lanes
+        // stride over the rows and the whole wave leaves together
+        rb = rows + b * nO * SCPQP_OBST_NP;
+        bool bad = false;
+        for (int o = lane; o < nO; o += WAVE) bad |= scpqp_obst_dev::bad_row(rb + o * SCPQP_OBST_NP);
+        if (__any(bad)) return;
+    } else {
+        for (int o = lane; o < nO; o += WAVE) sincos(P->obst[o][2], &ocs[o][1], &ocs[o][0]);
+    }
 
     Best bv{INFINITY, 0x7fffffff, 0x7fffffff}, bo{INFINITY, 0x7fffffff, 0x7fffffff};
     double mv = INFINITY, mo = INFINITY;    // margins
@@ -206,10 +233,17 @@ __global__ __launch_bounds__(WAVE) void metrics_kernel(const DevConst* __restric
             const int v = q / nO, o = q - v * nO;
             const double* pa = pose[kk * nV + v];
             const Rect A{pa[0], pa[1], pa[2], pa[3], P->hx[v], P->hy[v]};
-            const double* ob = P->obst[o];
             const double t = (double)(tick0 + k) * P->tick_length;
-            const Rect O{t * ob[3] * ocs[o][0] + ob[0], t * ob[3] * ocs[o][1] + ob[1], ocs[o][0],
+            Rect O;
+            if constexpr (kRows) {
+                const double* ob = rb + o * SCPQP_OBST_NP;
+                const scpqp_obst_dev::Pose q = scpqp_obst_dev::pose_at(ob, t);
+                O = Rect{q.x, q.y, q.c, q.s, ob[SCPQP_OBST_LENGTH] * 0.5, ob[SCPQP_OBST_WIDTH] * 0.5};
+            } else {
+                const double* ob = P->obst[o];
+                O = Rect{t * ob[3] * ocs[o][0] + ob[0], t * ob[3] * ocs[o][1] + ob[1], ocs[o][0],
                          ocs[o][1], ob[4] * 0.5, ob[5] * 0.5};
+            }
             const double g = footprint_gap(A, O);
             if (dense.gap_obs) dense.gap_obs[(b * K + k) * nVO + q] = g;
             if (k >= k_first) {
@@ -371,6 +405,10 @@ int fill_const(const scpqp_metrics_params* p, DevConst* c) {
     return 0;
 }
 
+int accumulate(scpqp_metrics* m, int32_t B, int32_t n_ticks, int32_t tick0, int32_t k_first,
+               const double* x_path, const scpqp_metrics_acc* acc, const scpqp_metrics_dense* dense,
+               const int32_t* variant, bool with_rows, const double* rows, void* stream);
+
 }  // namespace
 
 extern "C" {
@@ -465,6 +503,28 @@ int scpqp_metrics_accumulate_variants(scpqp_metrics* m, int32_t B, int32_t n_tic
                                       const scpqp_metrics_acc* acc,
                                       const scpqp_metrics_dense* dense, const int32_t* variant,
                                       void* stream) {
+    return accumulate(m, B, n_ticks, tick0, k_first, x_path, acc, dense, variant, false, nullptr,
+                      stream);
+}
+
+int scpqp_metrics_accumulate_obstacles(scpqp_metrics* m, int32_t B, int32_t n_ticks, int32_t tick0,
+                                       int32_t k_first, const double* x_path,
+                                       const scpqp_metrics_acc* acc,
+                                       const scpqp_metrics_dense* dense, const int32_t* variant,
+                                       const double* rows, void* stream) {
+    return accumulate(m, B, n_ticks, tick0, k_first, x_path, acc, dense, variant, true, rows,
+                      stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// the one body of the three accumulate entry points; with_rows: the obstacle rows of
+// include/scpqp_obstacles.h pose the obstacles (rows non-NULL once there is work)
+int accumulate(scpqp_metrics* m, int32_t B, int32_t n_ticks, int32_t tick0, int32_t k_first,
+               const double* x_path, const scpqp_metrics_acc* acc, const scpqp_metrics_dense* dense,
+               const int32_t* variant, bool with_rows, const double* rows, void* stream) {
     if (B < 0 || n_ticks < 0) return scpqp_fail_(SCPQP_E_ARG, "batch size / n_ticks < 0");
     if (tick0 < 0) return scpqp_fail_(SCPQP_E_ARG, "tick0 < 0");
     if (k_first != 0 && k_first != 1) return scpqp_fail_(SCPQP_E_ARG, "k_first must be 0 or 1");
@@ -472,6 +532,10 @@ int scpqp_metrics_accumulate_variants(scpqp_metrics* m, int32_t B, int32_t n_tic
     if ((long long)tick0 + n_ticks > 0x7fffffffLL)
         return scpqp_fail_(SCPQP_E_SIZE, "tick0 + n_ticks too large");
     if (!m) return scpqp_fail_(SCPQP_E_ARG, "null metrics handle");
+    if (with_rows && m->n_obst < 1)
+        return scpqp_fail_(SCPQP_E_ARG, "obstacle rows on a handle without obstacles");
+    if (with_rows && (long long)B * m->n_obst * SCPQP_OBST_NP > 0x7fffffffLL)
+        return scpqp_fail_(SCPQP_E_SIZE, "B * n_obst too large");
     const long long per_tick = (long long)m->n_veh * NX > (long long)m->n_veh * m->n_obst
                                    ? (long long)m->n_veh * NX : (long long)m->n_veh * m->n_obst;
     const long long widest = per_tick > m->n_pair ? per_tick : m->n_pair;
@@ -482,17 +546,22 @@ int scpqp_metrics_accumulate_variants(scpqp_metrics* m, int32_t B, int32_t n_tic
         return scpqp_fail_(SCPQP_E_ARG, "nothing to do: null accumulator and no dense output");
     if (B == 0) return 0;
     if (!x_path) return scpqp_fail_(SCPQP_E_ARG, "null array");
+    if (with_rows && !rows) return scpqp_fail_(SCPQP_E_ARG, "null rows array");
     if (acc)
         if (int rc = check_acc(acc)) return rc;
     hipError_t e = hipSetDevice(m->device);
     if (e != hipSuccess) return scpqp_fail_(SCPQP_E_HIP, hipGetErrorString(e));
     const scpqp_metrics_acc a = acc ? *acc : scpqp_metrics_acc{};
     const scpqp_metrics_dense d = dense ? *dense : scpqp_metrics_dense{};
-    hipLaunchKernelGGL(metrics_kernel, dim3((unsigned)B), dim3(WAVE), 0,
-                       static_cast<hipStream_t>(stream), m->dev, m->n_var, variant, n_ticks, tick0, k_first,
-                       x_path, a,
-                       acc != nullptr, d);
+    if (with_rows)
+        hipLaunchKernelGGL(metrics_kernel<true>, dim3((unsigned)B), dim3(WAVE), 0,
+                           static_cast<hipStream_t>(stream), m->dev, m->n_var, variant, n_ticks,
+                           tick0, k_first, x_path, a, acc != nullptr, d, rows);
+    else
+        hipLaunchKernelGGL(metrics_kernel<false>, dim3((unsigned)B), dim3(WAVE), 0,
+                           static_cast<hipStream_t>(stream), m->dev, m->n_var, variant, n_ticks,
+                           tick0, k_first, x_path, a, acc != nullptr, d, nullptr);
     return launched();
 }
 
-}  // extern "C"
+}  // namespace

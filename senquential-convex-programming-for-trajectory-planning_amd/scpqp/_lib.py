@@ -1,6 +1,6 @@
 """ctypes binding of ``include/scpqp.h``, ``include/scpqp_noise.h``,
-``include/scpqp_metrics.h``, ``include/scpqp_variants.h`` and ``include/scpqp_truth.h``
-(the C-ABI of the HIP library).
+``include/scpqp_metrics.h``, ``include/scpqp_variants.h``, ``include/scpqp_truth.h`` and
+``include/scpqp_obstacles.h`` (the C-ABI of the HIP library).
 
 The shared library ``libscpqp.so`` is built in-tree (``__graft_entry__.build()``
 or ``python -m scpqp.build``).  There is no CPU fallback: if the library or a
@@ -154,6 +154,25 @@ class TruthDist(C.Structure):
 # every symbol include/scpqp_truth.h declares (checked by tests/test_truth_host.py)
 TRUTH_EXPORTS = ("scpqp_plant_step_truth", "scpqp_truth_fill_nominal", "scpqp_truth_sample")
 
+OBST_NP = 7
+(OBST_X, OBST_Y, OBST_HEADING, OBST_SPEED, OBST_LENGTH, OBST_WIDTH,
+ OBST_YAW_RATE) = range(OBST_NP)
+OBSTACLE_FIELDS = ("x", "y", "heading", "speed", "length", "width", "yaw_rate")
+NOISE_SITE_OBSTACLE = 4
+
+
+class ObstacleDist(C.Structure):
+    """scpqp_obstacles_dist (include/scpqp_obstacles.h)."""
+    _fields_ = [("n_obst", C.c_int32), ("pad0", C.c_int32),
+                ("mean", (C.c_double * MAX_OBST) * OBST_NP), ("field", TruthField * OBST_NP),
+                ("seed", C.c_uint64), ("b_offset", C.c_uint32), ("pad1", C.c_uint32)]
+
+
+# every symbol include/scpqp_obstacles.h declares (checked by tests/test_obstacles_host.py)
+OBSTACLE_EXPORTS = ("scpqp_obstacles_predict", "scpqp_obstacles_pose",
+                    "scpqp_obstacles_fill_nominal", "scpqp_obstacles_sample",
+                    "scpqp_metrics_accumulate_obstacles")
+
 _lib = None
 
 
@@ -239,6 +258,19 @@ def load(path=None):
         lib.scpqp_truth_fill_nominal.restype = C.c_int
         lib.scpqp_truth_sample.argtypes = [C.POINTER(TruthDist), C.c_int32, V, V]
         lib.scpqp_truth_sample.restype = C.c_int
+    # likewise an A/B build from before the obstacle truth
+    if path is None or hasattr(lib, "scpqp_obstacles_predict"):
+        D, I = C.c_double, C.c_int32
+        lib.scpqp_obstacles_predict.argtypes = [I, I, I, V, D, D, D, V, V]
+        lib.scpqp_obstacles_predict.restype = C.c_int
+        lib.scpqp_obstacles_pose.argtypes = [I, I, V, D, I, I, V, V]
+        lib.scpqp_obstacles_pose.restype = C.c_int
+        lib.scpqp_obstacles_fill_nominal.argtypes = [I, _dp, I, V, V]
+        lib.scpqp_obstacles_fill_nominal.restype = C.c_int
+        lib.scpqp_obstacles_sample.argtypes = [C.POINTER(ObstacleDist), I, V, V]
+        lib.scpqp_obstacles_sample.restype = C.c_int
+        lib.scpqp_metrics_accumulate_obstacles.argtypes = [H, I, I, I, I, V, MA, MD, V, V, V]
+        lib.scpqp_metrics_accumulate_obstacles.restype = C.c_int
     if path is None:
         _lib = lib
     return lib

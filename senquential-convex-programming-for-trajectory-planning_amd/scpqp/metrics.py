@@ -133,7 +133,7 @@ class PathMetrics:
         LB.check(self.lib.scpqp_metrics_reset(self.h, B, C.byref(self._acc), self._stream()),
                  self.lib)
 
-    def accumulate(self, x_path, tick0, k_first, dense=False, variant=None):
+    def accumulate(self, x_path, tick0, k_first, dense=False, variant=None, obstacles=None):
         """Merge one step's path ``x_path`` [B, nVeh, K, 6] (a float64 device tensor, the
         output of ``plant.plant_step``; entry k is global tick ``tick0 + k``) over its
         entries ``k_first..K-1``.  ``dense=True`` also returns this call's ``gap_veh``
@@ -141,7 +141,10 @@ class PathMetrics:
         every entry; ``dense="only"`` returns them and leaves the accumulator alone.
         ``variant`` [B] int: realisation b is measured against entry ``variant[b]`` of the
         table of ``set_variants`` (None: entry 0); with an index outside the table the
-        realisation's accumulator and dense rows are left as they are."""
+        realisation's accumulator and dense rows are left as they are.
+        ``obstacles`` [B, nObst, 7] (scpqp/obstacles.py; include/scpqp_obstacles.h): obstacle
+        o of realisation b moves and is sized by its own row instead of the scenario's
+        constant obstacle; a realisation with a bad row is left as it is."""
         if x_path.dtype != torch.float64 or x_path.device != self.device or x_path.dim() != 4:
             raise ValueError("x_path must be a float64 [B, nVeh, K, 6] tensor on the metrics' device")
         B, V, K, nx = (int(s) for s in x_path.shape)
@@ -165,7 +168,24 @@ class PathMetrics:
                                 gap_obs=out["gap_obs"].data_ptr() if self.nO else None,
                                 xtrack=out["xtrack"].data_ptr())
         acc = None if dense == "only" else C.byref(self._acc)
-        if var is None:
+        if obstacles is not None:
+            rows = obstacles
+            if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float64 \
+                    or rows.device != self.device:
+                raise ValueError("obstacles must be a float64 tensor on the metrics' device")
+            if not self.nO:
+                raise ValueError("obstacles given, but the scenario has no obstacles")
+            if tuple(rows.shape) != (B, self.nO, LB.OBST_NP):
+                raise ValueError(f"obstacles must be [B, nObst, 7] = [{B}, {self.nO}, 7], got "
+                                 f"{list(rows.shape)}")
+            rows = rows.contiguous()
+            LB.check(self.lib.scpqp_metrics_accumulate_obstacles(
+                self.h, B, K - 1, int(tick0), int(k_first), C.c_void_p(x.data_ptr()), acc,
+                None if D is None else C.byref(D),
+                None if var is None else C.c_void_p(var.data_ptr()),
+                C.c_void_p(rows.data_ptr()), self._stream()), self.lib)
+            self._last_variant, self._last_rows = var, rows   # alive until the stream has read them
+        elif var is None:
             LB.check(self.lib.scpqp_metrics_accumulate(
                 self.h, B, K - 1, int(tick0), int(k_first), C.c_void_p(x.data_ptr()), acc,
                 None if D is None else C.byref(D), self._stream()), self.lib)

@@ -26,7 +26,9 @@ counter-based generator (include/scpqp_noise.h), reproducible from the seed and
 independent of how the realisations are sharded.  ``noise=`` instead holds a
 caller-made constant pair per vehicle over the whole rollout.  ``reset(..., truth=)``
 gives the plant of every (realisation, vehicle) its own geometry, steering lag, gain and
-offset (include/scpqp_truth.h), unknown to the controller.
+offset (include/scpqp_truth.h), unknown to the controller.  ``reset(..., obstacles=)``
+gives every (realisation, obstacle) its own start pose, speed, footprint and turn rate
+(include/scpqp_obstacles.h); the controller extrapolates what it measures on a straight line.
 """
 from __future__ import annotations
 
@@ -179,7 +181,8 @@ class ClosedLoopBatch:
         self.state = torch.zeros((self.B, self.nV, 6), **f)
         self.last_path = None          # [B, nV, tps + 1, 6] of the previous step
         self.u_prev = None
-        self.trace = trace      # keep every step's solve inputs and per-SCP-iteration trace
+        self.obst_rows = None          # the obstacle truth of reset(..., obstacles=)
+        self.trace = trace     # keep every step's solve inputs and per-SCP-iteration trace
         self.out = self.solver.alloc_out(self.B, trace=trace)
         self.history = []
         # realised-path metrics (scpqp/metrics.py); off: nothing is allocated or launched
@@ -188,7 +191,8 @@ class ClosedLoopBatch:
             from .metrics import PathMetrics
             self.path_metrics = PathMetrics(scenario, self.B, self.device, variants=self.variants)
 
-    def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0, truth=None):
+    def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0, truth=None,
+              obstacles=None):
         """main.py:73-75: vehiclePathFullRes[:, v, 0] = x0; the control path holds
         scenario.u0 for the first ticks_delay_u + ticks_per_sim + 1 ticks.
 
@@ -202,7 +206,25 @@ class ClosedLoopBatch:
         realises the path has these parameters per (realisation, vehicle).  Only the plant
         step reads them: the delay compensation, the solve, the steering limit and the
         evaluation keep the scenario's nominal model (main.py:121-123).  Validated here,
-        before anything is launched; None: nothing is allocated and the nominal kernels run."""
+        before anything is launched; None: nothing is allocated and the nominal kernels run.
+
+        ``obstacles`` [B, nObst, 7] (scpqp/obstacles.py; include/scpqp_obstacles.h): every
+        (realisation, obstacle) moves by its own row: start pose, speed, footprint and a
+        constant turn rate.  The controller measures the true pose and extrapolates it on a
+        straight line, on the device (scpqp_obstacles_predict); the metrics and
+        ``result_for_plot`` follow the row.  With ``variants`` the rows replace the variants'
+        obstacle sets and the dsafe tables stay per variant.  Validated here, before anything
+        is launched: a refused reset changes nothing.  None: the scenario's constant
+        obstacles, predicted on the host as before."""
+        if obstacles is not None:
+            from . import obstacles as OB
+            if not self.nO:
+                raise ValueError("obstacles given, but the scenario has no obstacles")
+            o = obstacles.detach().cpu().numpy() if isinstance(obstacles, torch.Tensor) \
+                else np.asarray(obstacles, float)
+            if tuple(o.shape) != (self.B, self.nO, OB.NP):
+                raise ValueError(f"obstacles must be [B, nObst, 7] = [{self.B}, {self.nO}, 7]")
+            OB.validate(o)
         if truth is not None:
             from . import truth as TR
             t = truth.detach().cpu().numpy() if isinstance(truth, torch.Tensor) \
@@ -229,6 +251,8 @@ class ClosedLoopBatch:
                                                                 device=self.device)
         self.truth = None if truth is None else torch.as_tensor(
             truth, dtype=torch.float64, device=self.device).contiguous()
+        self.obst_rows = None if obstacles is None else torch.as_tensor(
+            obstacles, dtype=torch.float64, device=self.device).contiguous().clone()
         self.last_path = None
         self.u_prev = None
         self.history = []
@@ -242,6 +266,13 @@ class ClosedLoopBatch:
         realisation of a variant.  Returns a device tensor [B, nObst, 2, Hp] or None."""
         if not self.nO:
             return None
+        if self.obst_rows is not None:
+            # the obstacle truth: the true pose at the measurement tick, extrapolated
+            # straight, per (realisation, obstacle) on the device
+            from . import obstacles as OB
+            sc = self.sc
+            return OB.predict(self.obst_rows, tick_meas * sc.tick_length,
+                              sc.delay_x + sc.dt + sc.delay_u, sc.dt, self.Hp)
         if self.var_obstacles is not None:
             # one prediction per variant on the host, gathered per realisation on the device
             fut = np.stack([self._predict(ob, tick_meas) for ob in self.var_obstacles])
@@ -318,7 +349,7 @@ class ClosedLoopBatch:
         if self.path_metrics is not None:
             # every global tick once: entry 0 of a later step is the previous step's last
             self.path_metrics.accumulate(path, tick0=i * tps, k_first=0 if i == 0 else 1,
-                                         variant=self.variant_of)
+                                         variant=self.variant_of, obstacles=self.obst_rows)
         self.last_path = path
         self.state = path[:, :, tps, :].contiguous()
         rec = dict(x0=x0, u0=u_hold, umax=umax, U=U, traj=out.traj.clone(),
@@ -326,6 +357,8 @@ class ClosedLoopBatch:
         if rng is not None:
             rec["ec_noise"] = ec_noise
             rec["epoch"] = i
+        if self.obst_rows is not None:
+            rec["obst"] = obst      # what the controller was told of the obstacle truth
         if self.evaluate:
             # main.py:201-202: evaluateInOriginalProblem on the clipped U and the prediction
             ref = self.solver.sample_reference(x0, variant=self.variant_of)
@@ -375,7 +408,12 @@ class ClosedLoopBatch:
         veh = np.full((6, nV, T + 1), np.nan)
         veh[:, :, 0] = self.x_init[b].cpu().numpy().T
         obs = np.zeros((self.nO, 2, T + 1))
-        if self.nO:
+        if self.obst_rows is not None:
+            # the realisation's own obstacle motion (include/scpqp_obstacles.h)
+            from . import obstacles as OB
+            p = OB.pose(self.obst_rows[b:b + 1], sc.tick_length, 0, T)[0].cpu().numpy()
+            obs[:, 0], obs[:, 1] = p[:, :, 0], p[:, :, 1]
+        elif self.nO:
             t = np.arange(T + 1) * sc.tick_length                       # main.py:61-71
             ob = self.obstacles
             obs[:, 0] = t[None] * (ob[:, 3] * np.cos(ob[:, 2]))[:, None] + ob[:, 0:1]

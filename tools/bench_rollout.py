@@ -1,7 +1,7 @@
 """Closed-loop Monte-Carlo rollout throughput (main.py:98-206).
 
 GPU: ``ClosedLoopBatch`` over B realisations (perturbed initial states of the
-4-vehicle circle scenario, Hp 20) for S MPC steps: delay compensation, warm-
+4-vehicle circle scenario, Hp 20, unless ``--scenario`` names another) for S MPC steps: delay compensation, warm-
 started SCP solve, clipping, plant step and evaluateInOriginalProblem per step.
 CPU: the restatement ``oracle.plant_reference.ClosedLoop`` (the reference's
 scipy calls + the structured SCP restatement) on a bounded sample, one
@@ -9,6 +9,8 @@ realisation per spawned single-threaded worker.
 
     python tools/bench_rollout.py [B] [steps] [cpu_sample] [--noise-seed S] [--metrics]
                                   [--variants K] [--mismatch PCT [--truth-seed S]]
+                                  [--scenario {circle4,frog,parallel5}]
+                                  [--obstacle-yaw W [--obstacle-seed S]]
 
 Prints one JSON line: realisation-steps/s on the GPU and the CPU, and the
 largest state difference between the two on the CPU sample.  ``--noise-seed S``
@@ -27,6 +29,15 @@ realisations with that realisation's value.
 ``--metrics`` and prints the summary beside that of the same batch with the nominal plant
 (``metrics_nominal``, an untimed second run); with ``--variants K`` both per value.  The CPU
 sample stays nominal, so the state difference then shows the mismatch.
+``--scenario`` picks the scenario: ``circle4`` (the default: 4 vehicles, Hp 20, no obstacles),
+``frog`` (1 vehicle, 22 moving obstacles, Hp 10) or ``parallel5`` (5 vehicles, 4 standing
+obstacles, Hp 10).  ``--variants`` sweeps the circle scenario only.
+``--obstacle-yaw W`` runs the timed batch with an obstacle truth (include/scpqp_obstacles.h):
+every (realisation, obstacle) draws a constant turn rate uniformly in +-W rad/s on the device
+from ``--obstacle-seed`` (default 1); the controller extrapolates what it measures on a
+straight line, on the device.  ``W = 0`` gives the nominal rows: the scenario's own
+obstacles, predicted on the device instead of on the host.  It implies ``--metrics``; the CPU
+sample keeps the straight obstacles.
 """
 import json
 import multiprocessing as mp
@@ -40,6 +51,16 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "senquential-convex-programming-for-tra
 import numpy as np  # noqa: E402
 
 SIGMA = np.array([0.05, 0.05, 0.005, 0.02, 0.0, 0.002])
+SCENARIOS = ("circle4", "frog", "parallel5")
+
+
+def make_scenario(name):
+    from oracle import scp_reference as R
+    if name == "frog":
+        return R.frog_scenario(Hp=10)
+    if name == "parallel5":
+        return R.parallel_scenario(5, Hp=10)
+    return R.circle_scenario(4, Hp=20)
 
 
 def initial_states(sc, B, seed=0):
@@ -52,9 +73,8 @@ def _cpu_worker(args):
     os.environ["OMP_NUM_THREADS"] = "1"
     sys.path[:0] = [ROOT, os.path.join(ROOT, "senquential-convex-programming-for-trajectory-planning_amd")]
     from oracle import plant_reference as PR
-    from oracle import scp_reference as R
-    x_init, steps, hp, dsafe_extra = args
-    sc = R.circle_scenario(4, Hp=hp)
+    x_init, steps, name, dsafe_extra = args
+    sc = make_scenario(name)
     if dsafe_extra is not None:
         sc.dsafeExtra = dsafe_extra
     cl = PR.ClosedLoop(sc, x_init=x_init)
@@ -91,16 +111,38 @@ def main():
         del argv[at:at + 2]
         if mismatch is None:
             raise SystemExit("--truth-seed needs --mismatch PCT")
+    name = "circle4"
+    if "--scenario" in argv:
+        at = argv.index("--scenario")
+        name = argv[at + 1]
+        del argv[at:at + 2]
+        if name not in SCENARIOS:
+            raise SystemExit(f"--scenario: one of {', '.join(SCENARIOS)}")
+        if n_var and name != "circle4":
+            raise SystemExit("--variants sweeps the circle scenario only")
+    obstacle_yaw, obstacle_seed = None, 1
+    if "--obstacle-yaw" in argv:
+        at = argv.index("--obstacle-yaw")
+        obstacle_yaw = float(argv[at + 1])
+        del argv[at:at + 2]
+    if "--obstacle-seed" in argv:
+        at = argv.index("--obstacle-seed")
+        obstacle_seed = int(argv[at + 1], 0)
+        del argv[at:at + 2]
+        if obstacle_yaw is None:
+            raise SystemExit("--obstacle-seed needs --obstacle-yaw W")
     metrics = "--metrics" in argv
     if metrics:
         argv.remove("--metrics")
-    metrics = metrics or n_var > 0 or mismatch is not None
+    metrics = metrics or n_var > 0 or mismatch is not None or obstacle_yaw is not None
     B = int(argv[0]) if len(argv) > 0 else 1024
     steps = int(argv[1]) if len(argv) > 1 else 5
     cpu_n = int(argv[2]) if len(argv) > 2 else 16
-    hp = 20
     from oracle import scp_reference as R
-    sc = R.circle_scenario(4, Hp=hp)
+    sc = make_scenario(name)
+    hp = sc.Hp
+    if obstacle_yaw is not None and not sc.nObst:
+        raise SystemExit(f"--obstacle-yaw: the scenario {name} has no obstacles")
     x_init = initial_states(sc, B)
     cpu_n = min(cpu_n, B)
     variants = variant_of = None
@@ -116,7 +158,7 @@ def main():
         extras = [float(values[k]) for k in variant_of]
     t0 = time.perf_counter()
     with mp.get_context("spawn").Pool(cpu_n) as pool:
-        cpu = pool.map(_cpu_worker, [(x_init[b], steps, hp, extras[b]) for b in range(cpu_n)])
+        cpu = pool.map(_cpu_worker, [(x_init[b], steps, name, extras[b]) for b in range(cpu_n)])
     cpu_wall = time.perf_counter() - t0
 
     import torch
@@ -127,10 +169,15 @@ def main():
     if mismatch is not None:
         from scpqp.truth import TruthDist
         truth = TruthDist(sc, truth_seed).relative(mismatch).sample(B, device="cuda")
-    cl.reset(x_init, seed=noise_seed, truth=truth)
+    rows = None
+    if obstacle_yaw is not None:
+        from scpqp.obstacles import ObstacleDist
+        rows = ObstacleDist(sc, obstacle_seed).uniform("yaw_rate", obstacle_yaw).sample(
+            B, device="cuda")
+    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows)
     cl.run(1)                      # warm-up (library load, first launches)
     torch.cuda.synchronize()
-    cl.reset(x_init, seed=noise_seed, truth=truth)
+    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     hist = cl.run(steps)
@@ -141,7 +188,9 @@ def main():
     feas = float(np.mean([h["evaluation"]["predictionFeasible"].float().mean().item() for h in hist]))
     summary = cl.metrics_summary() if metrics else None
     out = {
-        "metric": "closed-loop MPC realisation-steps/s (4 veh, Hp=20)",
+        "metric": "closed-loop MPC realisation-steps/s (4 veh, Hp=20)" if name == "circle4" else
+                  f"closed-loop MPC realisation-steps/s ({name}: {sc.nVeh} veh, {sc.nObst} obst, "
+                  f"Hp={hp})",
         "gpu_value": B * steps / gpu_s, "gpu_ms_per_step": gpu_s / steps * 1e3, "batch": B,
         "steps": steps, "noise_seed": noise_seed,
         "cpu_value": cpu_n * steps / cpu_wall, "cpu_workers": cpu_n,
@@ -157,10 +206,12 @@ def main():
         from scpqp.metrics import summarize_by_variant
         by = summarize_by_variant(cl.metrics(), variant_of)
         out["variants"] = [{"dsafe_extra": float(values[k]), "metrics": by[k]} for k in sorted(by)]
+    if obstacle_yaw is not None:
+        out["scenario"], out["obstacle_yaw"], out["obstacle_seed"] = name, obstacle_yaw, obstacle_seed
     if mismatch is not None:
         # the same batch with the nominal plant, untimed: what the mismatch costs
         out["mismatch_pct"], out["truth_seed"] = mismatch, truth_seed
-        cl.reset(x_init, seed=noise_seed)
+        cl.reset(x_init, seed=noise_seed, obstacles=rows)
         cl.run(steps)
         out["metrics_nominal"] = cl.metrics_summary()
         if n_var:

@@ -1,6 +1,6 @@
 """ctypes binding of ``include/scpqp.h``, ``include/scpqp_noise.h``,
-``include/scpqp_metrics.h``, ``include/scpqp_variants.h``, ``include/scpqp_truth.h`` and
-``include/scpqp_obstacles.h`` (the C-ABI of the HIP library).
+``include/scpqp_metrics.h``, ``include/scpqp_variants.h``, ``include/scpqp_truth.h``,
+``include/scpqp_obstacles.h`` and ``include/scpqp_sensing.h`` (the C-ABI of the HIP library).
 
 The shared library ``libscpqp.so`` is built in-tree (``__graft_entry__.build()``
 or ``python -m scpqp.build``).  There is no CPU fallback: if the library or a
@@ -173,6 +173,32 @@ OBSTACLE_EXPORTS = ("scpqp_obstacles_predict", "scpqp_obstacles_pose",
                     "scpqp_obstacles_fill_nominal", "scpqp_obstacles_sample",
                     "scpqp_metrics_accumulate_obstacles")
 
+SENSE_NP = 8
+(SENSE_SIG_POS, SENSE_SIG_HEADING, SENSE_SIG_SPEED, SENSE_SIG_STEER, SENSE_BIAS_HEADING,
+ SENSE_SCALE_SPEED, SENSE_P_DROP, SENSE_LAG) = range(SENSE_NP)
+SENSE_FIELDS = ("sig_pos", "sig_heading", "sig_speed", "sig_steer", "bias_heading", "scale_speed",
+                "p_drop", "lag")
+OSENSE_NP = 3
+OSENSE_FIELDS = ("sig_pos", "sig_heading", "sig_speed")
+NOISE_SITE_SENSE, NOISE_SITE_SENSE_DRAW, NOISE_SITE_SENSE_OBST = 5, 6, 7
+
+
+class SenseStream(C.Structure):
+    """scpqp_sense_stream (include/scpqp_sensing.h)."""
+    _fields_ = [("seed", C.c_uint64), ("epoch", C.c_uint32), ("b_offset", C.c_uint32)]
+
+
+class SenseDist(C.Structure):
+    """scpqp_sense_dist (include/scpqp_sensing.h)."""
+    _fields_ = [("n_veh", C.c_int32), ("pad0", C.c_int32),
+                ("mean", (C.c_double * MAX_VEH) * SENSE_NP), ("field", TruthField * SENSE_NP),
+                ("seed", C.c_uint64), ("b_offset", C.c_uint32), ("pad1", C.c_uint32)]
+
+
+# every symbol include/scpqp_sensing.h declares (checked by tests/test_sensing_host.py)
+SENSE_EXPORTS = ("scpqp_sense_measure", "scpqp_sense_fill_nominal", "scpqp_sense_sample",
+                 "scpqp_obstacles_predict_sensed")
+
 _lib = None
 
 
@@ -271,6 +297,18 @@ def load(path=None):
         lib.scpqp_obstacles_sample.restype = C.c_int
         lib.scpqp_metrics_accumulate_obstacles.argtypes = [H, I, I, I, I, V, MA, MD, V, V, V]
         lib.scpqp_metrics_accumulate_obstacles.restype = C.c_int
+    # likewise an A/B build from before the sensing truth
+    if path is None or hasattr(lib, "scpqp_sense_measure"):
+        D, I = C.c_double, C.c_int32
+        SS = C.POINTER(SenseStream)
+        lib.scpqp_sense_measure.argtypes = [I, I, I, I, V, V, SS, V, V, V, V]
+        lib.scpqp_sense_measure.restype = C.c_int
+        lib.scpqp_sense_fill_nominal.argtypes = [I, I, V, V]
+        lib.scpqp_sense_fill_nominal.restype = C.c_int
+        lib.scpqp_sense_sample.argtypes = [C.POINTER(SenseDist), I, V, V]
+        lib.scpqp_sense_sample.restype = C.c_int
+        lib.scpqp_obstacles_predict_sensed.argtypes = [I, I, I, V, V, SS, D, D, D, V, V]
+        lib.scpqp_obstacles_predict_sensed.restype = C.c_int
     if path is None:
         _lib = lib
     return lib

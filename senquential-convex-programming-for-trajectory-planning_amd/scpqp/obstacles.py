@@ -15,6 +15,9 @@ The controller measures the true pose and extrapolates it on a straight line
 ``validate``      host-side check of the rows before a rollout
 ``predict``       the controller's prediction [B, nObst, 2, Hp] of one MPC step
 ``pose``          x, y, heading of every row over a range of global ticks
+
+``scpqp.sensing.predict_sensed`` is ``predict`` from a noisy measurement of the pose and speed
+(include/scpqp_sensing.h).
 """
 from __future__ import annotations
 

@@ -29,6 +29,8 @@ gives the plant of every (realisation, vehicle) its own geometry, steering lag, 
 offset (include/scpqp_truth.h), unknown to the controller.  ``reset(..., obstacles=)``
 gives every (realisation, obstacle) its own start pose, speed, footprint and turn rate
 (include/scpqp_obstacles.h); the controller extrapolates what it measures on a straight line.
+``reset(..., sensing=, obstacle_sensing=)`` makes what the controller measures of the vehicles
+and the obstacles noisy, biased, late or lost (include/scpqp_sensing.h).
 """
 from __future__ import annotations
 
@@ -182,6 +184,9 @@ class ClosedLoopBatch:
         self.last_path = None          # [B, nV, tps + 1, 6] of the previous step
         self.u_prev = None
         self.obst_rows = None          # the obstacle truth of reset(..., obstacles=)
+        self.sense_rows = None         # the sensing truth of reset(..., sensing=)
+        self.osense_rows = None        # and of reset(..., obstacle_sensing=)
+        self.x_held = None
         self.trace = trace     # keep every step's solve inputs and per-SCP-iteration trace
         self.out = self.solver.alloc_out(self.B, trace=trace)
         self.history = []
@@ -192,7 +197,7 @@ class ClosedLoopBatch:
             self.path_metrics = PathMetrics(scenario, self.B, self.device, variants=self.variants)
 
     def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0, truth=None,
-              obstacles=None):
+              obstacles=None, sensing=None, obstacle_sensing=None, sense_seed=None):
         """main.py:73-75: vehiclePathFullRes[:, v, 0] = x0; the control path holds
         scenario.u0 for the first ticks_delay_u + ticks_per_sim + 1 ticks.
 
@@ -215,7 +220,43 @@ class ClosedLoopBatch:
         ``result_for_plot`` follow the row.  With ``variants`` the rows replace the variants'
         obstacle sets and the dsafe tables stay per variant.  Validated here, before anything
         is launched: a refused reset changes nothing.  None: the scenario's constant
-        obstacles, predicted on the host as before."""
+        obstacles, predicted on the host as before.
+
+        ``sensing`` [B, nVeh, 8] (scpqp/sensing.py; include/scpqp_sensing.h): what the
+        controller measures of every (realisation, vehicle) is noisy, biased, scaled, late or
+        lost, drawn per step on the device from ``sense_seed`` (epoch i, realisation
+        ``b_offset + b``).  Only the measurement changes: the steering limit keeps reading the
+        realised speed, and the delay compensation, the solve, the plant and the metrics are
+        what they were.  ``obstacle_sensing`` [B, nObst, 3]: noise on the obstacle pose and
+        speed the controller extrapolates; it needs ``obstacles=`` rows, which stay the truth
+        of the world.  Both are validated here, before anything is launched; None: the lines
+        of the exact sensor run, and nothing is allocated."""
+        if sensing is not None or obstacle_sensing is not None:
+            from . import sensing as SE
+            if sense_seed is not None and not 0 <= int(sense_seed) < 2 ** 64:
+                raise ValueError("sense_seed must be in [0, 2**64)")
+            if not 0 <= int(b_offset) < 2 ** 32:
+                raise ValueError("b_offset must be in [0, 2**32)")
+        if sensing is not None:
+            s = sensing.detach().cpu().numpy() if isinstance(sensing, torch.Tensor) \
+                else np.asarray(sensing, float)
+            if tuple(s.shape) != (self.B, self.nV, SE.NP):
+                raise ValueError(f"sensing must be [B, nVeh, 8] = [{self.B}, {self.nV}, 8]")
+            # the measured tick k_meas - lag must lie in the previous step's path
+            SE.validate(s, max_lag=self.tps - self.tdx)
+            if sense_seed is None and not SE.is_nominal(s):
+                raise ValueError("sensing rows that draw need reset(..., sense_seed=...)")
+        if obstacle_sensing is not None:
+            if obstacles is None:
+                raise ValueError("obstacle_sensing needs obstacles= rows: pass "
+                                 "obstacles.nominal(scenario, B) for the scenario's own")
+            os_ = obstacle_sensing.detach().cpu().numpy() \
+                if isinstance(obstacle_sensing, torch.Tensor) else np.asarray(obstacle_sensing, float)
+            if tuple(os_.shape) != (self.B, self.nO, SE.ONP):
+                raise ValueError(f"obstacle_sensing must be [B, nObst, 3] = [{self.B}, {self.nO}, 3]")
+            SE.validate_obstacle_sensing(os_)
+            if sense_seed is None and os_.any():
+                raise ValueError("obstacle_sensing rows that draw need reset(..., sense_seed=...)")
         if obstacles is not None:
             from . import obstacles as OB
             if not self.nO:
@@ -253,6 +294,16 @@ class ClosedLoopBatch:
             truth, dtype=torch.float64, device=self.device).contiguous()
         self.obst_rows = None if obstacles is None else torch.as_tensor(
             obstacles, dtype=torch.float64, device=self.device).contiguous().clone()
+        self.sense_rows = None if sensing is None else torch.as_tensor(
+            sensing, dtype=torch.float64, device=self.device).contiguous().clone()
+        self.osense_rows = None if obstacle_sensing is None else torch.as_tensor(
+            obstacle_sensing, dtype=torch.float64, device=self.device).contiguous().clone()
+        # without a seed every row is nominal or zero and draws nothing
+        self.sense_seed = 0 if sense_seed is None else int(sense_seed)
+        self.sense_offset = int(b_offset)
+        # the last delivered measurement: NaN, so the first one is always delivered
+        self.x_held = None if sensing is None else torch.full(
+            (self.B, self.nV, 6), float("nan"), dtype=torch.float64, device=self.device)
         self.last_path = None
         self.u_prev = None
         self.history = []
@@ -271,6 +322,12 @@ class ClosedLoopBatch:
             # straight, per (realisation, obstacle) on the device
             from . import obstacles as OB
             sc = self.sc
+            if self.osense_rows is not None:
+                # the sensing truth: the same extrapolation from a noisy pose and speed
+                from . import sensing as SE
+                return SE.predict_sensed(self.obst_rows, self.osense_rows, self.sense_seed, self.i,
+                                         self.sense_offset, tick_meas * sc.tick_length,
+                                         sc.delay_x + sc.dt + sc.delay_u, sc.dt, self.Hp)
             return OB.predict(self.obst_rows, tick_meas * sc.tick_length,
                               sc.delay_x + sc.dt + sc.delay_u, sc.dt, self.Hp)
         if self.var_obstacles is not None:
@@ -309,6 +366,17 @@ class ClosedLoopBatch:
             x_meas = self.state
         else:
             x_meas = self.last_path[:, :, tps - min(self.tdx, tick_now), :].contiguous()
+        delivered = None
+        if self.sense_rows is not None:
+            # the sensing truth: what the controller gets of that tick (include/scpqp_sensing.h)
+            from . import sensing as SE
+            delivered = torch.empty((B, nV), dtype=torch.int32, device=self.device)
+            if self.last_path is None:
+                x_meas = SE.measure(self.state.contiguous(), 0, self.sense_rows, self.sense_seed, i,
+                                    self.sense_offset, self.x_held, delivered)
+            else:
+                x_meas = SE.measure(self.last_path, tps - min(self.tdx, tick_now), self.sense_rows,
+                                    self.sense_seed, i, self.sense_offset, self.x_held, delivered)
         speed = self.state[:, :, 3]
         umax = torch.minimum(torch.full_like(speed, float(sc.mechanicalSteeringLimit)),
                              torch.atan(LATERAL_ACC_LIMIT * self.L[None, :] / speed ** 2))
@@ -359,6 +427,9 @@ class ClosedLoopBatch:
             rec["epoch"] = i
         if self.obst_rows is not None:
             rec["obst"] = obst      # what the controller was told of the obstacle truth
+        if self.sense_rows is not None:
+            rec["x_meas"] = x_meas  # what the controller was told of the vehicles
+            rec["delivered"] = delivered
         if self.evaluate:
             # main.py:201-202: evaluateInOriginalProblem on the clipped U and the prediction
             ref = self.solver.sample_reference(x0, variant=self.variant_of)

@@ -11,6 +11,8 @@ realisation per spawned single-threaded worker.
                                   [--variants K] [--mismatch PCT [--truth-seed S]]
                                   [--scenario {circle4,frog,parallel5}]
                                   [--obstacle-yaw W [--obstacle-seed S]]
+                                  [--sense-pos SIGMA [--sense-heading SIGMA] [--sense-drop P]
+                                   [--sense-seed S]]
 
 Prints one JSON line: realisation-steps/s on the GPU and the CPU, and the
 largest state difference between the two on the CPU sample.  ``--noise-seed S``
@@ -38,6 +40,13 @@ from ``--obstacle-seed`` (default 1); the controller extrapolates what it measur
 straight line, on the device.  ``W = 0`` gives the nominal rows: the scenario's own
 obstacles, predicted on the device instead of on the host.  It implies ``--metrics``; the CPU
 sample keeps the straight obstacles.
+``--sense-pos SIGMA`` runs the timed batch with a sensing truth (include/scpqp_sensing.h): every
+vehicle's measured position carries N(0, SIGMA^2) noise in x and in y, its measured heading
+``--sense-heading`` rad of noise, and a step's measurement is lost with probability
+``--sense-drop``; drawn on the device from ``--sense-seed`` (default 1).  ``SIGMA = 0`` with
+no other flag gives the nominal rows: the exact sensor, measured on the device.  It implies
+``--metrics`` and prints the summary beside that of the same batch with exact sensing
+(``metrics_exact_sensing``, an untimed second run).  The CPU sample senses exactly.
 """
 import json
 import multiprocessing as mp
@@ -131,10 +140,24 @@ def main():
         del argv[at:at + 2]
         if obstacle_yaw is None:
             raise SystemExit("--obstacle-seed needs --obstacle-yaw W")
+    sense = {"pos": None, "heading": 0.0, "drop": 0.0}
+    sense_seed = 1
+    for key in sense:
+        if f"--sense-{key}" in argv:
+            at = argv.index(f"--sense-{key}")
+            sense[key] = float(argv[at + 1])
+            del argv[at:at + 2]
+    if "--sense-seed" in argv:
+        at = argv.index("--sense-seed")
+        sense_seed = int(argv[at + 1], 0)
+        del argv[at:at + 2]
+    if sense["pos"] is None and (sense["heading"] or sense["drop"] or sense_seed != 1):
+        raise SystemExit("--sense-heading, --sense-drop and --sense-seed need --sense-pos SIGMA")
     metrics = "--metrics" in argv
     if metrics:
         argv.remove("--metrics")
-    metrics = metrics or n_var > 0 or mismatch is not None or obstacle_yaw is not None
+    metrics = metrics or n_var > 0 or mismatch is not None or obstacle_yaw is not None \
+        or sense["pos"] is not None
     B = int(argv[0]) if len(argv) > 0 else 1024
     steps = int(argv[1]) if len(argv) > 1 else 5
     cpu_n = int(argv[2]) if len(argv) > 2 else 16
@@ -174,10 +197,18 @@ def main():
         from scpqp.obstacles import ObstacleDist
         rows = ObstacleDist(sc, obstacle_seed).uniform("yaw_rate", obstacle_yaw).sample(
             B, device="cuda")
-    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows)
+    sense_kw = {}
+    if sense["pos"] is not None:
+        from scpqp import sensing as SE
+        srows = SE.nominal(B, sc.nVeh, device="cuda")
+        srows[..., SE.FIELDS.index("sig_pos")] = sense["pos"]
+        srows[..., SE.FIELDS.index("sig_heading")] = sense["heading"]
+        srows[..., SE.FIELDS.index("p_drop")] = sense["drop"]
+        sense_kw = dict(sensing=srows, sense_seed=sense_seed)
+    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw)
     cl.run(1)                      # warm-up (library load, first launches)
     torch.cuda.synchronize()
-    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows)
+    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     hist = cl.run(steps)
@@ -208,10 +239,19 @@ def main():
         out["variants"] = [{"dsafe_extra": float(values[k]), "metrics": by[k]} for k in sorted(by)]
     if obstacle_yaw is not None:
         out["scenario"], out["obstacle_yaw"], out["obstacle_seed"] = name, obstacle_yaw, obstacle_seed
+    if sense["pos"] is not None:
+        # the same batch with exact sensing, untimed: what the sensor costs
+        out["sense_pos"], out["sense_heading"], out["sense_drop"] = (sense["pos"], sense["heading"],
+                                                                      sense["drop"])
+        out["sense_seed"] = sense_seed
+        out["delivered_frac"] = float(np.mean([h["delivered"].float().mean().item() for h in hist]))
+        cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows)
+        cl.run(steps)
+        out["metrics_exact_sensing"] = cl.metrics_summary()
     if mismatch is not None:
         # the same batch with the nominal plant, untimed: what the mismatch costs
         out["mismatch_pct"], out["truth_seed"] = mismatch, truth_seed
-        cl.reset(x_init, seed=noise_seed, obstacles=rows)
+        cl.reset(x_init, seed=noise_seed, obstacles=rows, **sense_kw)
         cl.run(steps)
         out["metrics_nominal"] = cl.metrics_summary()
         if n_var:

@@ -1,6 +1,7 @@
 """ctypes binding of ``include/scpqp.h``, ``include/scpqp_noise.h``,
 ``include/scpqp_metrics.h``, ``include/scpqp_variants.h``, ``include/scpqp_truth.h``,
-``include/scpqp_obstacles.h`` and ``include/scpqp_sensing.h`` (the C-ABI of the HIP library).
+``include/scpqp_obstacles.h``, ``include/scpqp_sensing.h`` and ``include/scpqp_estimator.h``
+(the C-ABI of the HIP library).
 
 The shared library ``libscpqp.so`` is built in-tree (``__graft_entry__.build()``
 or ``python -m scpqp.build``).  There is no CPU fallback: if the library or a
@@ -199,6 +200,16 @@ class SenseDist(C.Structure):
 SENSE_EXPORTS = ("scpqp_sense_measure", "scpqp_sense_fill_nominal", "scpqp_sense_sample",
                  "scpqp_obstacles_predict_sensed")
 
+EST_NS = 5
+EST_NP = 8
+(EST_R_POS, EST_R_HEADING, EST_R_SPEED, EST_R_STEER, EST_Q_POS, EST_Q_HEADING, EST_Q_SPEED,
+ EST_Q_STEER) = range(EST_NP)
+EST_FIELDS = ("r_pos", "r_heading", "r_speed", "r_steer", "q_pos", "q_heading", "q_speed",
+              "q_steer")
+
+# every symbol include/scpqp_estimator.h declares (checked by tests/test_estimator_host.py)
+EST_EXPORTS = ("scpqp_est_step",)
+
 _lib = None
 
 
@@ -309,6 +320,11 @@ def load(path=None):
         lib.scpqp_sense_sample.restype = C.c_int
         lib.scpqp_obstacles_predict_sensed.argtypes = [I, I, I, V, V, SS, D, D, D, V, V]
         lib.scpqp_obstacles_predict_sensed.restype = C.c_int
+    # likewise an A/B build from before the state estimator
+    if path is None or hasattr(lib, "scpqp_est_step"):
+        D, I = C.c_double, C.c_int32
+        lib.scpqp_est_step.argtypes = [PP, I, I, D, D, V, V, V, V, V, V, V, V]
+        lib.scpqp_est_step.restype = C.c_int
     if path is None:
         _lib = lib
     return lib

@@ -31,6 +31,8 @@ gives every (realisation, obstacle) its own start pose, speed, footprint and tur
 (include/scpqp_obstacles.h); the controller extrapolates what it measures on a straight line.
 ``reset(..., sensing=, obstacle_sensing=)`` makes what the controller measures of the vehicles
 and the obstacles noisy, biased, late or lost (include/scpqp_sensing.h).
+``reset(..., estimator=)`` puts an extended Kalman filter per (realisation, vehicle) between
+that measurement and the delay compensation (include/scpqp_estimator.h).
 """
 from __future__ import annotations
 
@@ -187,6 +189,7 @@ class ClosedLoopBatch:
         self.sense_rows = None         # the sensing truth of reset(..., sensing=)
         self.osense_rows = None        # and of reset(..., obstacle_sensing=)
         self.x_held = None
+        self.est_rows = None           # the estimator tuning of reset(..., estimator=)
         self.trace = trace     # keep every step's solve inputs and per-SCP-iteration trace
         self.out = self.solver.alloc_out(self.B, trace=trace)
         self.history = []
@@ -197,7 +200,8 @@ class ClosedLoopBatch:
             self.path_metrics = PathMetrics(scenario, self.B, self.device, variants=self.variants)
 
     def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0, truth=None,
-              obstacles=None, sensing=None, obstacle_sensing=None, sense_seed=None):
+              obstacles=None, sensing=None, obstacle_sensing=None, sense_seed=None,
+              estimator=None):
         """main.py:73-75: vehiclePathFullRes[:, v, 0] = x0; the control path holds
         scenario.u0 for the first ticks_delay_u + ticks_per_sim + 1 ticks.
 
@@ -230,7 +234,23 @@ class ClosedLoopBatch:
         what they were.  ``obstacle_sensing`` [B, nObst, 3]: noise on the obstacle pose and
         speed the controller extrapolates; it needs ``obstacles=`` rows, which stay the truth
         of the world.  Both are validated here, before anything is launched; None: the lines
-        of the exact sensor run, and nothing is allocated."""
+        of the exact sensor run, and nothing is allocated.
+
+        ``estimator`` [B, nVeh, 8] (scpqp/estimator.py; include/scpqp_estimator.h): an extended
+        Kalman filter per (realisation, vehicle) takes the step's measurement, exact or of
+        ``sensing=``, and its estimate replaces the measurement as the input of the delay
+        compensation.  It predicts over the ticks since the previous measurement with the
+        nominal model and the commands this controller issued.  The steering limit keeps
+        reading the realised speed; the solve, the plant, the metrics and the evaluation are
+        what they were.  Validated here, before anything is launched; None: nothing is
+        allocated and the measurement goes to the delay compensation as before."""
+        if estimator is not None:
+            from . import estimator as EST
+            e = estimator.detach().cpu().numpy() if isinstance(estimator, torch.Tensor) \
+                else np.asarray(estimator, float)
+            if tuple(e.shape) != (self.B, self.nV, EST.NP):
+                raise ValueError(f"estimator must be [B, nVeh, 8] = [{self.B}, {self.nV}, 8]")
+            EST.validate(e)
         if sensing is not None or obstacle_sensing is not None:
             from . import sensing as SE
             if sense_seed is not None and not 0 <= int(sense_seed) < 2 ** 64:
@@ -304,6 +324,13 @@ class ClosedLoopBatch:
         # the last delivered measurement: NaN, so the first one is always delivered
         self.x_held = None if sensing is None else torch.full(
             (self.B, self.nV, 6), float("nan"), dtype=torch.float64, device=self.device)
+        self.est_rows = None if estimator is None else torch.as_tensor(
+            estimator, dtype=torch.float64, device=self.device).contiguous().clone()
+        self.est_x = self.est_cov = None
+        if estimator is not None:
+            # no lane is initialised; the span of step 0 is empty
+            self.est_x, self.est_cov = EST.alloc(self.B, self.nV, self.device)
+        self.est_tick = None           # the global tick of the previous step's measurement
         self.last_path = None
         self.u_prev = None
         self.history = []
@@ -377,6 +404,23 @@ class ClosedLoopBatch:
             else:
                 x_meas = SE.measure(self.last_path, tps - min(self.tdx, tick_now), self.sense_rows,
                                     self.sense_seed, i, self.sense_offset, self.x_held, delivered)
+        x_in, nis = x_meas, None
+        if self.est_rows is not None:
+            # the state estimator (include/scpqp_estimator.h): predict over the ticks
+            # (g0, g1] since the previous measurement, tick j with the control tick the
+            # plant's output j read (below), then correct with this step's measurement
+            from . import estimator as EST
+            g1 = max(0, tick_now - self.tdx)
+            g0 = g1 if self.est_tick is None else self.est_tick
+            u_span = None
+            if g1 > g0:
+                span = [min(self.ticks_total, j + 1) for j in range(g0 + 1, g1 + 1)]
+                u_span = self.control[:, :, torch.as_tensor(span, device=self.device)].contiguous()
+            x_meas = x_meas.contiguous()
+            nis = EST.step(self.params, u_span, sc.tick_length, x_meas, delivered, self.est_rows,
+                           self.est_x, self.est_cov, h_max=self.h_max)
+            self.est_tick = g1
+            x_in = self.est_x.clone()
         speed = self.state[:, :, 3]
         umax = torch.minimum(torch.full_like(speed, float(sc.mechanicalSteeringLimit)),
                              torch.atan(LATERAL_ACC_LIMIT * self.L[None, :] / speed ** 2))
@@ -386,7 +430,7 @@ class ClosedLoopBatch:
         horizon = sc.delay_x + sc.dt + sc.delay_u
         # with a seed: this step's noise stream (epoch i), else None and nothing changes
         rng = None if self.rng is None else self.rng.at(i)
-        x0, dtraj = PL.delay_compensate(self.params, x_meas.contiguous(), u_hold, horizon,
+        x0, dtraj = PL.delay_compensate(self.params, x_in.contiguous(), u_hold, horizon,
                                         noise=self.noise, h_max=self.h_max, device=self.device,
                                         rng=rng)
         # SCP solve, warm-started from the previous controller output (SCP_controller.py:42-43)
@@ -430,6 +474,11 @@ class ClosedLoopBatch:
         if self.sense_rows is not None:
             rec["x_meas"] = x_meas  # what the controller was told of the vehicles
             rec["delivered"] = delivered
+        if self.est_rows is not None:
+            rec["x_est"] = x_in     # what the controller planned from: a clone of the estimate
+            rec["nis"] = nis
+            if self.sense_rows is None:
+                rec["x_meas"] = x_meas.clone()
         if self.evaluate:
             # main.py:201-202: evaluateInOriginalProblem on the clipped U and the prediction
             ref = self.solver.sample_reference(x0, variant=self.variant_of)

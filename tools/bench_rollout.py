@@ -12,7 +12,9 @@ realisation per spawned single-threaded worker.
                                   [--scenario {circle4,frog,parallel5}]
                                   [--obstacle-yaw W [--obstacle-seed S]]
                                   [--sense-pos SIGMA [--sense-heading SIGMA] [--sense-drop P]
-                                   [--sense-seed S]]
+                                   [--sense-seed S]
+                                   [--estimate [--est-q-pos Q] [--est-q-heading Q]
+                                    [--est-q-speed Q] [--est-q-steer Q]]]
 
 Prints one JSON line: realisation-steps/s on the GPU and the CPU, and the
 largest state difference between the two on the CPU sample.  ``--noise-seed S``
@@ -47,6 +49,12 @@ vehicle's measured position carries N(0, SIGMA^2) noise in x and in y, its measu
 no other flag gives the nominal rows: the exact sensor, measured on the device.  It implies
 ``--metrics`` and prints the summary beside that of the same batch with exact sensing
 (``metrics_exact_sensing``, an untimed second run).  The CPU sample senses exactly.
+``--estimate`` (with ``--sense-pos``) puts the state estimator (include/scpqp_estimator.h) between
+that sensor and the planner in the timed run: ``estimator.matched`` rows of the ``--sense-*``
+sigmas, with the process-noise densities ``--est-q-pos``, ``--est-q-heading``, ``--est-q-speed``
+and ``--est-q-steer`` (default ``estimator.Q_DEFAULT``).  It reports three sets of metrics for
+the same batch: filtered (``metrics``, the timed run), raw noisy sensor (``metrics_raw_sensing``)
+and exact sensor (``metrics_exact_sensing``), each with its mean SCP iterations.
 """
 import json
 import multiprocessing as mp
@@ -153,6 +161,19 @@ def main():
         del argv[at:at + 2]
     if sense["pos"] is None and (sense["heading"] or sense["drop"] or sense_seed != 1):
         raise SystemExit("--sense-heading, --sense-drop and --sense-seed need --sense-pos SIGMA")
+    estimate = "--estimate" in argv
+    if estimate:
+        argv.remove("--estimate")
+    est_q = {"pos": None, "heading": None, "speed": None, "steer": None}
+    for key in est_q:
+        if f"--est-q-{key}" in argv:
+            at = argv.index(f"--est-q-{key}")
+            est_q[key] = float(argv[at + 1])
+            del argv[at:at + 2]
+            if not estimate:
+                raise SystemExit("--est-q-* needs --estimate")
+    if estimate and sense["pos"] is None:
+        raise SystemExit("--estimate needs --sense-pos SIGMA (its R is matched to the sensor)")
     metrics = "--metrics" in argv
     if metrics:
         argv.remove("--metrics")
@@ -205,10 +226,15 @@ def main():
         srows[..., SE.FIELDS.index("sig_heading")] = sense["heading"]
         srows[..., SE.FIELDS.index("p_drop")] = sense["drop"]
         sense_kw = dict(sensing=srows, sense_seed=sense_seed)
-    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw)
+    est_kw = {}
+    if estimate:
+        from scpqp import estimator as EST
+        q = [EST.Q_DEFAULT[k] if est_q[key] is None else est_q[key] for k, key in enumerate(est_q)]
+        est_kw = dict(estimator=EST.matched(srows, q=q))
+    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw)
     cl.run(1)                      # warm-up (library load, first launches)
     torch.cuda.synchronize()
-    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw)
+    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     hist = cl.run(steps)
@@ -245,13 +271,25 @@ def main():
                                                                       sense["drop"])
         out["sense_seed"] = sense_seed
         out["delivered_frac"] = float(np.mean([h["delivered"].float().mean().item() for h in hist]))
+        if estimate:
+            # the same batch and sensor without the filter, untimed: what the filter recovers
+            out["estimate"] = True
+            out["est_floor"], out["est_q"] = list(EST.FLOOR), q
+            nis = torch.cat([h["nis"].flatten() for h in hist])
+            out["mean_nis"] = float(nis[~torch.isnan(nis)].mean().item())
+            cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw)
+            raw = cl.run(steps)
+            out["metrics_raw_sensing"] = cl.metrics_summary()
+            out["mean_scp_iters_raw"] = float(np.mean([h["n_scp"].float().mean().item() for h in raw]))
         cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows)
-        cl.run(steps)
+        exact = cl.run(steps)
         out["metrics_exact_sensing"] = cl.metrics_summary()
+        out["mean_scp_iters_exact"] = float(np.mean([h["n_scp"].float().mean().item()
+                                                     for h in exact]))
     if mismatch is not None:
         # the same batch with the nominal plant, untimed: what the mismatch costs
         out["mismatch_pct"], out["truth_seed"] = mismatch, truth_seed
-        cl.reset(x_init, seed=noise_seed, obstacles=rows, **sense_kw)
+        cl.reset(x_init, seed=noise_seed, obstacles=rows, **sense_kw, **est_kw)
         cl.run(steps)
         out["metrics_nominal"] = cl.metrics_summary()
         if n_var:

@@ -1,7 +1,7 @@
 """ctypes binding of ``include/scpqp.h``, ``include/scpqp_noise.h``,
 ``include/scpqp_metrics.h``, ``include/scpqp_variants.h``, ``include/scpqp_truth.h``,
-``include/scpqp_obstacles.h``, ``include/scpqp_sensing.h`` and ``include/scpqp_estimator.h``
-(the C-ABI of the HIP library).
+``include/scpqp_obstacles.h``, ``include/scpqp_sensing.h``, ``include/scpqp_estimator.h`` and
+``include/scpqp_tracker.h`` (the C-ABI of the HIP library).
 
 The shared library ``libscpqp.so`` is built in-tree (``__graft_entry__.build()``
 or ``python -m scpqp.build``).  There is no CPU fallback: if the library or a
@@ -210,6 +210,18 @@ EST_FIELDS = ("r_pos", "r_heading", "r_speed", "r_steer", "q_pos", "q_heading", 
 # every symbol include/scpqp_estimator.h declares (checked by tests/test_estimator_host.py)
 EST_EXPORTS = ("scpqp_est_step",)
 
+TRK_NS = 5
+TRK_NZ = 4
+TRK_NP = 9
+(TRK_R_POS, TRK_R_HEADING, TRK_R_SPEED, TRK_Q_POS, TRK_Q_HEADING, TRK_Q_SPEED, TRK_Q_YAW,
+ TRK_P0_YAW, TRK_W_CLAMP) = range(TRK_NP)
+TRK_FIELDS = ("r_pos", "r_heading", "r_speed", "q_pos", "q_heading", "q_speed", "q_yaw",
+              "p0_yaw", "w_clamp")
+TRK_DSINC_SWITCH = 0.02
+
+# every symbol include/scpqp_tracker.h declares (checked by tests/test_tracker_host.py)
+TRK_EXPORTS = ("scpqp_obstacles_track",)
+
 _lib = None
 
 
@@ -325,6 +337,12 @@ def load(path=None):
         D, I = C.c_double, C.c_int32
         lib.scpqp_est_step.argtypes = [PP, I, I, D, D, V, V, V, V, V, V, V, V]
         lib.scpqp_est_step.restype = C.c_int
+    # likewise an A/B build from before the obstacle tracker
+    if path is None or hasattr(lib, "scpqp_obstacles_track"):
+        D, I = C.c_double, C.c_int32
+        SS = C.POINTER(SenseStream)
+        lib.scpqp_obstacles_track.argtypes = [I, I, I, V, V, SS, V, D, D, D, D, V, V, V, V, V, V]
+        lib.scpqp_obstacles_track.restype = C.c_int
     if path is None:
         _lib = lib
     return lib

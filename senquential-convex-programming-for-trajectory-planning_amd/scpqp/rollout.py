@@ -33,6 +33,8 @@ gives every (realisation, obstacle) its own start pose, speed, footprint and tur
 and the obstacles noisy, biased, late or lost (include/scpqp_sensing.h).
 ``reset(..., estimator=)`` puts an extended Kalman filter per (realisation, vehicle) between
 that measurement and the delay compensation (include/scpqp_estimator.h).
+``reset(..., tracker=)`` puts one per (realisation, obstacle) between the obstacle measurement
+and the obstacle prediction (include/scpqp_tracker.h).
 """
 from __future__ import annotations
 
@@ -190,6 +192,7 @@ class ClosedLoopBatch:
         self.osense_rows = None        # and of reset(..., obstacle_sensing=)
         self.x_held = None
         self.est_rows = None           # the estimator tuning of reset(..., estimator=)
+        self.trk_rows = None           # the tracker tuning of reset(..., tracker=)
         self.trace = trace     # keep every step's solve inputs and per-SCP-iteration trace
         self.out = self.solver.alloc_out(self.B, trace=trace)
         self.history = []
@@ -201,7 +204,7 @@ class ClosedLoopBatch:
 
     def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0, truth=None,
               obstacles=None, sensing=None, obstacle_sensing=None, sense_seed=None,
-              estimator=None):
+              estimator=None, tracker=None):
         """main.py:73-75: vehiclePathFullRes[:, v, 0] = x0; the control path holds
         scenario.u0 for the first ticks_delay_u + ticks_per_sim + 1 ticks.
 
@@ -243,7 +246,25 @@ class ClosedLoopBatch:
         nominal model and the commands this controller issued.  The steering limit keeps
         reading the realised speed; the solve, the plant, the metrics and the evaluation are
         what they were.  Validated here, before anything is launched; None: nothing is
-        allocated and the measurement goes to the delay compensation as before."""
+        allocated and the measurement goes to the delay compensation as before.
+
+        ``tracker`` [B, nObst, 9] (scpqp/tracker.py; include/scpqp_tracker.h): an extended
+        Kalman filter per (realisation, obstacle) takes the step's obstacle measurement, exact
+        or of ``obstacle_sensing=``, estimates the turn rate, and its prediction on the arc of
+        the estimate replaces the straight extrapolation as the solve's ``obst``.  It needs
+        ``obstacles=`` rows.  The world (metrics, plotted paths) keeps the true rows.
+        Validated here, before anything is launched; None: nothing is allocated or launched
+        and the prediction is what it was."""
+        if tracker is not None:
+            from . import tracker as TRK
+            if obstacles is None:
+                raise ValueError("tracker needs obstacles= rows: pass "
+                                 "obstacles.nominal(scenario, B) for the scenario's own")
+            tk = tracker.detach().cpu().numpy() if isinstance(tracker, torch.Tensor) \
+                else np.asarray(tracker, float)
+            if tuple(tk.shape) != (self.B, self.nO, TRK.NP):
+                raise ValueError(f"tracker must be [B, nObst, 9] = [{self.B}, {self.nO}, 9]")
+            TRK.validate(tk)
         if estimator is not None:
             from . import estimator as EST
             e = estimator.detach().cpu().numpy() if isinstance(estimator, torch.Tensor) \
@@ -331,6 +352,13 @@ class ClosedLoopBatch:
             # no lane is initialised; the span of step 0 is empty
             self.est_x, self.est_cov = EST.alloc(self.B, self.nV, self.device)
         self.est_tick = None           # the global tick of the previous step's measurement
+        self.trk_rows = None if tracker is None else torch.as_tensor(
+            tracker, dtype=torch.float64, device=self.device).contiguous().clone()
+        self.trk_x = self.trk_cov = None
+        if tracker is not None:
+            self.trk_x, self.trk_cov = TRK.alloc(self.B, self.nO, self.device)
+        self.trk_tick = None           # the global tick of the previous obstacle measurement
+        self.trk_rec = None            # this step's (estimate, nis, measurement)
         self.last_path = None
         self.u_prev = None
         self.history = []
@@ -349,6 +377,20 @@ class ClosedLoopBatch:
             # straight, per (realisation, obstacle) on the device
             from . import obstacles as OB
             sc = self.sc
+            if self.trk_rows is not None:
+                # the obstacle tracker (include/scpqp_tracker.h): the same measurement,
+                # filtered over the time since the previous one, predicted on its arc
+                from . import tracker as TRK
+                g0 = tick_meas if self.trk_tick is None else self.trk_tick
+                obst, z, nis = TRK.step(self.obst_rows, self.osense_rows, self.sense_seed, self.i,
+                                        self.sense_offset, self.trk_rows,
+                                        tick_meas * sc.tick_length,
+                                        (tick_meas - g0) * sc.tick_length,
+                                        sc.delay_x + sc.dt + sc.delay_u, sc.dt, self.Hp,
+                                        self.trk_x, self.trk_cov)
+                self.trk_tick = tick_meas
+                self.trk_rec = (self.trk_x.clone(), nis, z)
+                return obst
             if self.osense_rows is not None:
                 # the sensing truth: the same extrapolation from a noisy pose and speed
                 from . import sensing as SE
@@ -471,6 +513,9 @@ class ClosedLoopBatch:
             rec["epoch"] = i
         if self.obst_rows is not None:
             rec["obst"] = obst      # what the controller was told of the obstacle truth
+        if self.trk_rows is not None:
+            # the tracker's estimate, its innovations and the obstacle measurement it took
+            rec["obst_est"], rec["obst_nis"], rec["obst_meas"] = self.trk_rec
         if self.sense_rows is not None:
             rec["x_meas"] = x_meas  # what the controller was told of the vehicles
             rec["delivered"] = delivered

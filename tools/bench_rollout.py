@@ -15,6 +15,7 @@ realisation per spawned single-threaded worker.
                                    [--sense-seed S]
                                    [--estimate [--est-q-pos Q] [--est-q-heading Q]
                                     [--est-q-speed Q] [--est-q-steer Q]]]
+                                  [--track]
 
 Prints one JSON line: realisation-steps/s on the GPU and the CPU, and the
 largest state difference between the two on the CPU sample.  ``--noise-seed S``
@@ -55,6 +56,13 @@ sigmas, with the process-noise densities ``--est-q-pos``, ``--est-q-heading``, `
 and ``--est-q-steer`` (default ``estimator.Q_DEFAULT``).  It reports three sets of metrics for
 the same batch: filtered (``metrics``, the timed run), raw noisy sensor (``metrics_raw_sensing``)
 and exact sensor (``metrics_exact_sensing``), each with its mean SCP iterations.
+``--track`` (with ``--obstacle-yaw``) puts the obstacle tracker (include/scpqp_tracker.h) between
+the obstacle measurement and the obstacle prediction in the timed run.  The obstacle sensor of
+the batch is then (``--sense-pos``, ``--sense-heading``, 0) per obstacle, exact without
+``--sense-pos``, drawn from ``--sense-seed``; the tracker rows are ``tracker.matched`` of it.  It
+reports the timed, tracked run (``metrics``, ``gpu_ms_per_step``, ``mean_nis_obst``) next to the
+same batch and obstacle sensor without the tracker, run and timed after it
+(``metrics_untracked``, ``gpu_ms_per_step_untracked``, ``mean_scp_iters_untracked``).
 """
 import json
 import multiprocessing as mp
@@ -174,6 +182,11 @@ def main():
                 raise SystemExit("--est-q-* needs --estimate")
     if estimate and sense["pos"] is None:
         raise SystemExit("--estimate needs --sense-pos SIGMA (its R is matched to the sensor)")
+    track = "--track" in argv
+    if track:
+        argv.remove("--track")
+        if obstacle_yaw is None:
+            raise SystemExit("--track needs --obstacle-yaw W (it tracks the obstacle truth's rows)")
     metrics = "--metrics" in argv
     if metrics:
         argv.remove("--metrics")
@@ -231,10 +244,18 @@ def main():
         from scpqp import estimator as EST
         q = [EST.Q_DEFAULT[k] if est_q[key] is None else est_q[key] for k, key in enumerate(est_q)]
         est_kw = dict(estimator=EST.matched(srows, q=q))
-    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw)
+    trk_kw = {}
+    if track:
+        from scpqp import tracker as TRK
+        osense = torch.zeros((B, sc.nObst, 3), dtype=torch.float64, device="cuda")
+        if sense["pos"] is not None:
+            osense[..., 0], osense[..., 1] = sense["pos"], sense["heading"]
+        sense_kw = dict(sense_kw, obstacle_sensing=osense, sense_seed=sense_seed)
+        trk_kw = dict(tracker=TRK.matched(osense))
+    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw, **trk_kw)
     cl.run(1)                      # warm-up (library load, first launches)
     torch.cuda.synchronize()
-    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw)
+    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw, **trk_kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     hist = cl.run(steps)
@@ -265,6 +286,22 @@ def main():
         out["variants"] = [{"dsafe_extra": float(values[k]), "metrics": by[k]} for k in sorted(by)]
     if obstacle_yaw is not None:
         out["scenario"], out["obstacle_yaw"], out["obstacle_seed"] = name, obstacle_yaw, obstacle_seed
+    if track:
+        # the same batch and obstacle sensor without the tracker, timed as well
+        out["track"] = True
+        out["trk_floor"], out["trk_q"] = list(TRK.FLOOR), list(TRK.Q_DEFAULT)
+        out["trk_p0_yaw"], out["trk_w_clamp"] = TRK.P0_YAW, TRK.W_CLAMP
+        nis = torch.cat([h["obst_nis"].flatten() for h in hist])
+        out["mean_nis_obst"] = float(nis[~torch.isnan(nis)].mean().item())
+        cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        plain = cl.run(steps)
+        torch.cuda.synchronize()
+        out["gpu_ms_per_step_untracked"] = (time.perf_counter() - t0) / steps * 1e3
+        out["metrics_untracked"] = cl.metrics_summary()
+        out["mean_scp_iters_untracked"] = float(np.mean([h["n_scp"].float().mean().item()
+                                                         for h in plain]))
     if sense["pos"] is not None:
         # the same batch with exact sensing, untimed: what the sensor costs
         out["sense_pos"], out["sense_heading"], out["sense_drop"] = (sense["pos"], sense["heading"],
@@ -277,7 +314,7 @@ def main():
             out["est_floor"], out["est_q"] = list(EST.FLOOR), q
             nis = torch.cat([h["nis"].flatten() for h in hist])
             out["mean_nis"] = float(nis[~torch.isnan(nis)].mean().item())
-            cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw)
+            cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **trk_kw)
             raw = cl.run(steps)
             out["metrics_raw_sensing"] = cl.metrics_summary()
             out["mean_scp_iters_raw"] = float(np.mean([h["n_scp"].float().mean().item() for h in raw]))
@@ -289,7 +326,7 @@ def main():
     if mismatch is not None:
         # the same batch with the nominal plant, untimed: what the mismatch costs
         out["mismatch_pct"], out["truth_seed"] = mismatch, truth_seed
-        cl.reset(x_init, seed=noise_seed, obstacles=rows, **sense_kw, **est_kw)
+        cl.reset(x_init, seed=noise_seed, obstacles=rows, **sense_kw, **est_kw, **trk_kw)
         cl.run(steps)
         out["metrics_nominal"] = cl.metrics_summary()
         if n_var:

@@ -200,6 +200,27 @@ int scpqp_sample_reference(scpqp_handle* h, int32_t B, const scpqp_batch_in* in,
 int scpqp_resources(scpqp_handle* h, int64_t* lds_bytes, int64_t* ws_bytes_per_wg,
                     int32_t* big_mode, int32_t* grid);
 
+/* The memory plan and the solve-kernel instantiation of a shape (scpqp_plan_query). */
+typedef struct scpqp_plan_info {
+    int32_t plan;            /* 0 everything in LDS, 1 constraint vectors in the workspace,
+                                2 also the KKT factor (= scpqp_resources big_mode)         */
+    int32_t lean;            /* plan 1 with the W~ blocks and constraint rows in the
+                                workspace as well                                          */
+    int32_t per_cu;          /* workgroups per CU: grid = per_cu * the device's CU count   */
+    int32_t row_slots;       /* R = ceil((n_veh*hp_max + 1) / 64)                          */
+    int32_t shape;           /* compiled shape the sizes match (0: none); the kernel is
+                                compiled for it only where the plan matches too (sh)       */
+    int32_t hg, vg, rm, occ, sh;   /* the instantiation (HG, VG, RM, OCC, SH) a launch runs */
+    int64_t lds_bytes;       /* dynamic LDS per workgroup                                  */
+    int64_t ws_doubles_per_wg;     /* global workspace per workgroup, in doubles           */
+} scpqp_plan_info;
+
+/* What scpqp_create would plan for `dims`, and the kernel a call would run on that handle
+ * (has_hp: the call passes scpqp_batch_in.hp).  Applies scpqp_create's size checks and
+ * returns its error codes; needs no device and calls no HIP function.  The launch selects
+ * its kernel through the same function this reports. */
+int scpqp_plan_query(const scpqp_dims* dims, int32_t has_hp, scpqp_plan_info* out);
+
 /* Shape of scpqp_batch_out.trace for this handle: doubles per iteration and
  * iterations per problem (= the handle's max_scp_iter). */
 int scpqp_trace_layout(scpqp_handle* h, int32_t* stride_doubles, int32_t* iters);

@@ -109,8 +109,18 @@ const size_t kLdsGranule = 2048;
 // workgroups per CU at three waves per SIMD (the 168-VGPR budget of OCC = 3)
 const int kMaxPerCU = 12 / NWAVE;
 
-int plan(scpqp_handle* h) {
-    const int V = h->dims.n_veh, O = h->dims.n_obst, Hm = h->dims.hp_max;
+// The plan of a shape (n_veh, n_obst, hp_max): arithmetic on the sizes alone, with no handle
+// and no device (scpqp_plan_query reports it; plan() installs it in a handle).
+struct PlanShape {
+    int cfg = 0;         // 0, 1 or 2 (below)
+    bool lean = false;   // plan 1 with W~ and the constraint rows in the workspace too
+    int perCU = 0;       // workgroups per CU
+    int occ = 2;         // waves per SIMD the register budget is compiled for (template OCC)
+    size_t ldsBytes = 0;
+    long long ws = 0;    // workspace doubles per workgroup
+};
+
+int plan_shape(int V, int O, int Hm, PlanShape* ps) {
     // Plans: 0 everything in LDS, 1 constraint vectors in the workspace (lean at two
     // workgroups per CU: W~ and the constraint rows too), 2 also the KKT matrix.  The
     // register budget is compiled for 2 or 3 workgroups per CU (OCC), and the device
@@ -157,26 +167,96 @@ int plan(scpqp_handle* h) {
     if (const char* o4 = getenv("SCPQP_OCC4")) {
         const Off f = plan_offsets(V, O, Hm, false, true, true);
         if (atoi(o4) == 1 && (size_t)(f.persist + f.uni) * sizeof(double) * 4 <= kLdsLimit) {
-            h->hG = 0;
-            h->vG = 1;
-            h->ldsBytes = (size_t)(f.persist + f.uni) * sizeof(double);
-            h->wsStride = f.ws;
-            h->grid = h->cus * 4;
-            h->occ = 4;
+            ps->cfg = 1;
+            ps->lean = true;
+            ps->perCU = 4;
+            ps->occ = 4;
+            ps->ldsBytes = (size_t)(f.persist + f.uni) * sizeof(double);
+            ps->ws = f.ws;
             return 0;
         }
     }
 #endif
     if (best < 0) return fail(SCPQP_E_SIZE, "problem too large for the LDS plan%s");
     const Off f = plan_offsets(V, O, Hm, best >= 2, best >= 1, bestLean);
-    h->hG = best >= 2;
-    h->vG = best >= 1;
-    h->ldsBytes = (size_t)(f.persist + f.uni) * sizeof(double);
-    h->wsStride = f.ws;
-    h->grid = h->cus * bestPer;
+    ps->cfg = best;
+    ps->lean = bestLean;
+    ps->perCU = bestPer;
     // waves per SIMD the register budget is compiled for (template OCC)
-    h->occ = (bestPer * NWAVE + 3) / 4 >= 3 ? 3 : 2;
+    ps->occ = (bestPer * NWAVE + 3) / 4 >= 3 ? 3 : 2;
+    ps->ldsBytes = (size_t)(f.persist + f.uni) * sizeof(double);
+    ps->ws = f.ws;
     return 0;
+}
+
+// the handle's part of the plan: the grid, from its device's CU count
+int plan(scpqp_handle* h) {
+    PlanShape ps;
+    if (const int rc = plan_shape(h->dims.n_veh, h->dims.n_obst, h->dims.hp_max, &ps)) return rc;
+    h->hG = ps.cfg >= 2;
+    h->vG = ps.cfg >= 1;
+    h->ldsBytes = ps.ldsBytes;
+    h->wsStride = ps.ws;
+    h->grid = h->cus * ps.perCU;
+    h->occ = ps.occ;
+    return 0;
+}
+
+// the size checks of scpqp_create and scpqp_plan_query
+int check_dims(const scpqp_dims* dims) {
+    if (dims->n_veh < 1 || dims->n_veh > SCPQP_MAX_VEH) return fail(SCPQP_E_ARG, "n_veh out of range%s");
+    if (dims->n_obst < 0 || dims->n_obst > SCPQP_MAX_OBST) return fail(SCPQP_E_ARG, "n_obst out of range%s");
+    if (dims->hp_max < 1 || dims->hp_max > SCPQP_MAX_HP) return fail(SCPQP_E_ARG, "hp_max out of range%s");
+    if (dims->n_veh * dims->hp_max + 1 > 256) return fail(SCPQP_E_SIZE, "n_veh*hp_max+1 > 256%s");
+    if (dims->max_batch < 0) return fail(SCPQP_E_ARG, "max_batch < 0%s");
+    return 0;
+}
+
+// A kernel instantiation (HG, VG, RM, OCC, SH) as one integer: what select_kernel returns,
+// launch switches on and scpqp_plan_query decodes.
+constexpr int kernel_id(bool hg, bool vg, int rm, int occ, int sh) {
+    return (hg ? 1 << 13 : 0) | (vg ? 1 << 12 : 0) | rm << 8 | occ << 4 | sh;
+}
+
+// row slots of the triangular solves: the n = n_veh * hp_max + 1 rows in slots of 64
+int row_slots(const scpqp_dims& d) { return (d.n_veh * d.hp_max + 1 + 63) / 64; }
+
+// compile-time shapes (shape_c): the BASELINE configurations' instantiations
+int compiled_shape(const scpqp_dims& d, bool has_hp) {
+    int sh = 0;
+    if (d.n_obst == 0 && d.n_veh == 4) sh = (d.hp_max == 20 && !has_hp) ? 1 : 2;
+    if (d.n_obst == 0 && d.n_veh == 8 && d.hp_max == 30 && !has_hp) sh = 3;
+#ifdef SCPQP_DIAG
+    if (const char* e = getenv("SCPQP_SHAPE"))   // diagnostic build: SCPQP_SHAPE=0 runs the runtime shape
+        if (atoi(e) == 0) sh = 0;
+#endif
+    return sh;
+}
+
+// The instantiation a launch runs, from the sizes, the plan (hG, vG, occ: waves per SIMD the
+// register budget is compiled for) and whether the call passes a per-problem horizon array.
+// The one selection: launch switches on its result, scpqp_plan_query reports it.
+int select_kernel(const scpqp_dims& d, bool hG, bool vG, int occ, bool has_hp) {
+    const int R = row_slots(d);
+    const int sh = compiled_shape(d, has_hp);
+    if (sh == 1 && !hG && vG && R == 2 && occ == 3) return kernel_id(false, true, 2, 3, 1);
+#ifdef SCPQP_DIAG
+    if (sh == 1 && !hG && vG && R == 2 && occ == 4) return kernel_id(false, true, 2, 4, 1);
+#endif
+    if (sh == 2 && vG && R == 2 && occ == 3) return kernel_id(hG, true, 2, 3, 2);
+    if (sh == 2 && !hG && vG && R == 2 && occ == 2) return kernel_id(false, true, 2, 2, 2);
+    if (sh == 3 && hG && R == 4 && occ == 2) return kernel_id(true, true, 4, 2, 3);
+    const bool vg = hG || vG;   // a factor in the workspace runs the (true, true) kernels
+    switch (R * 4 + occ) {
+        case 6: return kernel_id(hG, vg, 1, 2, 0);
+        case 7: return kernel_id(hG, vg, 1, 3, 0);
+        case 10: return kernel_id(hG, vg, 2, 2, 0);
+        case 11: return kernel_id(hG, vg, 2, 3, 0);
+        case 14: return kernel_id(hG, vg, 3, 2, 0);
+        case 15: return kernel_id(hG, vg, 3, 3, 0);
+        case 19: return kernel_id(hG, vg, 4, 3, 0);
+        default: return kernel_id(hG, vg, 4, 2, 0);
+    }
 }
 
 typedef int (*KernelLaunch)(const void*, size_t, hipStream_t, int);
@@ -185,7 +265,6 @@ int run_kernel(KernelLaunch fn, scpqp_handle* h, const KArgs& a, hipStream_t st,
     if (e != 0) return fail(SCPQP_E_HIP, "HIP error: %s", hipGetErrorString(static_cast<hipError_t>(e)));
     return 0;
 }
-#define SCPQP_RUN(HG, VG, RM, OCC, SH) run_kernel(scpqp_kern::launch<HG, VG, RM, OCC, SH>, h, a, st, grid)
 
 // the kernel groups' diagnostic counters, summed (diag_read)
 int diag_sum(int what, unsigned long long* out, int count, int n, int reset) {
@@ -243,42 +322,17 @@ int launch(scpqp_handle* h, KArgs& a, hipStream_t st) {
         HIPCHK(hipGetLastError());
         a.perm = h->perm;
     }
-    const int R = (h->dims.n_veh * h->dims.hp_max + 1 + 63) / 64;   // row slots of the solves
-    const int occ = h->occ;   // waves per SIMD the register budget is compiled for
-    // compile-time shapes (shape_c): the BASELINE configurations' instantiations
-    const scpqp_dims& d = h->dims;
-    int sh = 0;
-    if (d.n_obst == 0 && d.n_veh == 4) sh = (d.hp_max == 20 && !a.hp) ? 1 : 2;
-    if (d.n_obst == 0 && d.n_veh == 8 && d.hp_max == 30 && !a.hp) sh = 3;
+    switch (select_kernel(h->dims, h->hG, h->vG, h->occ, a.hp != nullptr)) {
+#define SCPQP_CASE(HG, VG, RM, OCC, SH)  \
+    case kernel_id(HG, VG, RM, OCC, SH): \
+        return run_kernel(scpqp_kern::launch<HG, VG, RM, OCC, SH>, h, a, st, grid);
+        SCPQP_KERNEL_LIST(SCPQP_CASE)
 #ifdef SCPQP_DIAG
-    if (const char* e = getenv("SCPQP_SHAPE"))   // diagnostic build: SCPQP_SHAPE=0 runs the runtime shape
-        if (atoi(e) == 0) sh = 0;
+        SCPQP_CASE(false, true, 2, 4, 1)
 #endif
-    if (sh == 1 && !h->hG && h->vG && R == 2 && occ == 3) return SCPQP_RUN(false, true, 2, 3, 1);
-#ifdef SCPQP_DIAG
-    if (sh == 1 && !h->hG && h->vG && R == 2 && occ == 4) return SCPQP_RUN(false, true, 2, 4, 1);
-#endif
-    if (sh == 2 && h->vG && R == 2 && occ == 3) {
-        if (h->hG) return SCPQP_RUN(true, true, 2, 3, 2);
-        return SCPQP_RUN(false, true, 2, 3, 2);
+#undef SCPQP_CASE
     }
-    if (sh == 2 && !h->hG && h->vG && R == 2 && occ == 2) return SCPQP_RUN(false, true, 2, 2, 2);
-    if (sh == 3 && h->hG && R == 4 && occ == 2) return SCPQP_RUN(true, true, 4, 2, 3);
-#define SCPQP_DISPATCH(HGV, VGV)                                              \
-    switch (R * 4 + occ) {                                                   \
-        case 6: return SCPQP_RUN(HGV, VGV, 1, 2, 0);          \
-        case 7: return SCPQP_RUN(HGV, VGV, 1, 3, 0);          \
-        case 10: return SCPQP_RUN(HGV, VGV, 2, 2, 0);         \
-        case 11: return SCPQP_RUN(HGV, VGV, 2, 3, 0);         \
-        case 14: return SCPQP_RUN(HGV, VGV, 3, 2, 0);         \
-        case 15: return SCPQP_RUN(HGV, VGV, 3, 3, 0);         \
-        case 19: return SCPQP_RUN(HGV, VGV, 4, 3, 0);         \
-        default: return SCPQP_RUN(HGV, VGV, 4, 2, 0);         \
-    }
-    if (h->hG) { SCPQP_DISPATCH(true, true) }
-    if (h->vG) { SCPQP_DISPATCH(false, true) }
-    SCPQP_DISPATCH(false, false)
-#undef SCPQP_DISPATCH
+    return fail(SCPQP_E_SIZE, "no kernel instantiation for this plan%s");
 }
 
 // need_obst: the entry point reads the obstacle predictions (solve, evaluate);
@@ -398,11 +452,7 @@ const char* scpqp_version(void) { return "scpqp-mi355x 0.4 (gfx950, fp64)"; }
 int scpqp_create(const scpqp_dims* dims, const scpqp_params* p, int device, scpqp_handle** out) {
     if (!dims || !p || !out) return fail(SCPQP_E_ARG, "null argument%s");
     *out = nullptr;
-    if (dims->n_veh < 1 || dims->n_veh > SCPQP_MAX_VEH) return fail(SCPQP_E_ARG, "n_veh out of range%s");
-    if (dims->n_obst < 0 || dims->n_obst > SCPQP_MAX_OBST) return fail(SCPQP_E_ARG, "n_obst out of range%s");
-    if (dims->hp_max < 1 || dims->hp_max > SCPQP_MAX_HP) return fail(SCPQP_E_ARG, "hp_max out of range%s");
-    if (dims->n_veh * dims->hp_max + 1 > 256) return fail(SCPQP_E_SIZE, "n_veh*hp_max+1 > 256%s");
-    if (dims->max_batch < 0) return fail(SCPQP_E_ARG, "max_batch < 0%s");
+    if (const int rc = check_dims(dims)) return rc;
     if (const int rc = check_params(*dims, p)) return rc;
     scpqp_handle* h = new (std::nothrow) scpqp_handle();
     if (!h) return fail(SCPQP_E_NOMEM, "out of host memory%s");
@@ -565,6 +615,28 @@ int scpqp_resources(scpqp_handle* h, int64_t* lds, int64_t* ws, int32_t* big, in
     if (ws) *ws = (int64_t)h->wsStride * (int64_t)sizeof(double);
     if (big) *big = h->hG ? 2 : (h->vG ? 1 : 0);
     if (grid) *grid = h->grid;
+    return 0;
+}
+
+int scpqp_plan_query(const scpqp_dims* dims, int32_t has_hp, scpqp_plan_info* out) {
+    if (!dims || !out) return fail(SCPQP_E_ARG, "null argument%s");
+    memset(out, 0, sizeof(*out));
+    if (const int rc = check_dims(dims)) return rc;
+    PlanShape ps;
+    if (const int rc = plan_shape(dims->n_veh, dims->n_obst, dims->hp_max, &ps)) return rc;
+    const int id = select_kernel(*dims, ps.cfg >= 2, ps.cfg >= 1, ps.occ, has_hp != 0);
+    out->plan = ps.cfg;
+    out->lean = ps.lean;
+    out->per_cu = ps.perCU;
+    out->row_slots = row_slots(*dims);
+    out->shape = compiled_shape(*dims, has_hp != 0);
+    out->hg = (id >> 13) & 1;
+    out->vg = (id >> 12) & 1;
+    out->rm = (id >> 8) & 15;
+    out->occ = (id >> 4) & 15;
+    out->sh = id & 15;
+    out->lds_bytes = (int64_t)ps.ldsBytes;
+    out->ws_doubles_per_wg = (int64_t)ps.ws;
     return 0;
 }
 

@@ -81,10 +81,18 @@ class PlantParams(C.Structure):
                 ("lr", C.c_double * MAX_VEH)]
 
 
+class PlanInfo(C.Structure):
+    """scpqp_plan_info (include/scpqp.h): the plan and kernel instantiation of a shape."""
+    _fields_ = [("plan", C.c_int32), ("lean", C.c_int32), ("per_cu", C.c_int32),
+                ("row_slots", C.c_int32), ("shape", C.c_int32), ("hg", C.c_int32),
+                ("vg", C.c_int32), ("rm", C.c_int32), ("occ", C.c_int32), ("sh", C.c_int32),
+                ("lds_bytes", C.c_int64), ("ws_doubles_per_wg", C.c_int64)]
+
+
 # every symbol include/scpqp.h declares (checked by tests/test_abi.py)
 EXPORTS = ("scpqp_create", "scpqp_destroy", "scpqp_last_error", "scpqp_version", "scpqp_solve",
            "scpqp_linearize", "scpqp_evaluate", "scpqp_sample_reference", "scpqp_resources",
-           "scpqp_trace_layout",
+           "scpqp_trace_layout", "scpqp_plan_query",
            "scpqp_delay_compensate", "scpqp_plant_step", "scpqp_clip_controls")
 
 
@@ -259,6 +267,10 @@ def load(path=None):
     lib.scpqp_resources.restype = C.c_int
     lib.scpqp_trace_layout.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.scpqp_trace_layout.restype = C.c_int
+    # an explicit ``path`` may name an A/B build from before the plan query
+    if path is None or hasattr(lib, "scpqp_plan_query"):
+        lib.scpqp_plan_query.argtypes = [C.POINTER(Dims), C.c_int32, C.POINTER(PlanInfo)]
+        lib.scpqp_plan_query.restype = C.c_int
     PP = C.POINTER(PlantParams)
     V = C.c_void_p
     lib.scpqp_delay_compensate.argtypes = [PP, C.c_int32, C.c_double, C.c_int32, V, V, V, V, V,

@@ -340,6 +340,21 @@ class ScpQpSolver:
         return ref
 
 
+def plan_query(n_veh, n_obst, hp_max, has_hp=False):
+    """The memory plan and the solve-kernel instantiation ``(HG, VG, RM, OCC, SH)`` that a
+    solver of these sizes runs (``scpqp_plan_query``); ``has_hp``: the call passes a
+    per-problem horizon array.  Needs no GPU.  Raises RuntimeError where the constructor
+    would refuse the sizes."""
+    lib = LB.load()
+    D = LB.Dims(n_veh=int(n_veh), hp_max=int(hp_max), n_obst=int(n_obst), max_batch=0)
+    info = LB.PlanInfo()
+    LB.check(lib.scpqp_plan_query(C.byref(D), int(bool(has_hp)), C.byref(info)), lib)
+    d = {name: getattr(info, name) for name, _ in LB.PlanInfo._fields_}
+    d["lean"] = bool(d["lean"])
+    d["kernel"] = (info.hg, info.vg, info.rm, info.occ, info.sh)
+    return d
+
+
 def _need(t, n, what):
     """Exact element count of an optional device input (None passes)."""
     if t is not None and t.numel() != n:

@@ -1,0 +1,176 @@
+"""The case table of the dispatch tests: one row for every solve-kernel instantiation
+``(HG, VG, RM, OCC, SH)`` that the host plan (csrc/scpqp.hip: plan_shape, select_kernel) can
+reach, with the smallest scenario found that runs it.  Shared by tests/test_dispatch_host.py
+(CPU: the table against ``scpqp_plan_query`` over every accepted shape, and the input
+conditions below on the oracle alone) and tests/test_gpu_dispatch.py (GPU: parity of every
+row's kernel with the oracle).
+
+Inputs: the 8 problems ``BT.make_batch(sc, 8, base_seed=303)`` with every vehicle's start
+position scaled along its own reference line, ``x0[:, :, 0:2] *= s``.  With the stock circle
+start (s = 1) the short-horizon, many-vehicle shapes converge in two SCP iterations with no
+active collision row, and any kernel passes; nearer the centre (s < 1) the vehicles
+interact within a short horizon, while the long-horizon 6- and 7-vehicle shapes run into the
+20-iteration cap at s = 1 and stay clear of it a little further out (s > 1).  Each row's
+``s`` is chosen so that the ORACLE ALONE meets, on all 8 problems (pinned by
+test_dispatch_host.py::test_case_inputs_exercise_the_solver):
+
+  * every QP certified (the oracle raises UncertifiedQP otherwise);
+  * no problem at the 20-iteration cap;
+  * n_scp >= 3;
+  * the last QP has an active collision row, |b - A z| < 1e-7;
+  * the one-QP reference is unambiguous: the oracle's two polish modes (the reference's
+    exact KKT polish and the restatement of the device's regularised one) agree on the
+    first QP to 1e-9 rad, a tenth of the one-QP tolerance.
+
+The last condition is there because the first QP, linearised at u = 0, can be grossly
+infeasible (slack 6 to 9 with 14 to 18 active rows on 7 vehicles at Hp 28, s = 1.1).  On such
+a QP the regularised polish lands up to 1.9e-4 rad from the exact minimiser, in the
+restatement as on the device (the device's one-QP error there equals the restatement's
+mode spread: 1.9e-4 rad at 7 x 28, s = 1.1, and 7.8e-8 rad at 6 x 22, s = 1.3, problem 0, where
+the device reports SCPQP_FL_POLISH_REJECTED and the exact oracle certifies or not with the
+BLAS thread count).  The full solves of those inputs still agree to 3e-9 rad.  A reference
+whose own modes differ by more than the tolerance cannot hold a kernel to it, so the rows
+use s = 1.15 and 1.35, where the modes agree.
+"""
+from __future__ import annotations
+
+import os
+import sys
+from dataclasses import dataclass
+
+import numpy as np
+
+N_PROBLEMS = 8
+BASE_SEED = 303
+ACTIVE_TOL = 1e-7
+ONE_QP_MODE_SPREAD = 1e-9    # rad: a tenth of the one-QP tolerance (test_gpu_parity.QP_TOL)
+
+
+@dataclass(frozen=True)
+class Case:
+    kernel: tuple            # (HG, VG, RM, OCC, SH)
+    scenario: str            # "circle" or "frog"
+    n_veh: int
+    hp_max: int
+    has_hp: bool = False     # the call passes a per-problem horizon array
+    s: float = 1.0           # start-position scale (module docstring)
+    hps: tuple = None        # with has_hp: problem g runs at hps[g % len(hps)]
+    covered_by: str = None   # the parity test from before this table that runs the kernel;
+                             # None: tests/test_gpu_dispatch.py is its parity test
+    mixed: tuple = None      # a further mixed-horizon run: (n_veh, hp_max, horizons, s)
+
+    @property
+    def id(self):
+        return "k" + "".join(str(int(v)) for v in self.kernel) + \
+            f"_{self.scenario}{self.n_veh}x{self.hp_max}" + ("_hp" if self.has_hp else "")
+
+
+CASES = (
+    # --- instantiations that earlier parity tests run: identity and workgroup reuse here
+    Case((0, 1, 2, 3, 1), "circle", 4, 20, covered_by="test_gpu_parity: c2"),
+    Case((0, 1, 2, 3, 2), "circle", 4, 20, has_hp=True, hps=(20, 10, 15),
+         covered_by="test_gpu_parity: test_edge_cases (c2 with a horizon array)"),
+    Case((0, 1, 2, 2, 2), "circle", 4, 30, has_hp=True, hps=(10, 20, 30),
+         covered_by="test_gpu_configs: c5"),
+    Case((1, 1, 4, 2, 3), "circle", 8, 30, covered_by="test_gpu_configs: c3"),
+    Case((0, 0, 1, 3, 0), "frog", 1, 10, covered_by="test_gpu_parity: frog, golden c1"),
+    Case((0, 1, 1, 3, 0), "frog", 1, 20, covered_by="test_gpu_parity: frog_mixed, parallel5"),
+    Case((0, 0, 2, 3, 0), "circle", 1, 64, covered_by="test_gpu_parity: test_edge_cases"),
+    # --- instantiations no earlier parity test runs
+    Case((0, 0, 1, 2, 0), "frog", 1, 22),
+    Case((0, 1, 1, 2, 0), "frog", 1, 29, mixed=(1, 29, (29, 15, 5), 1.0)),
+    Case((0, 0, 2, 2, 0), "circle", 3, 28),
+    Case((0, 1, 2, 3, 0), "circle", 8, 8, s=0.5),
+    # parallel5 at Hp 14 (test_gpu_parity) runs this kernel for one QP, never a full solve
+    Case((0, 1, 2, 2, 0), "circle", 13, 5, s=0.5, mixed=(13, 5, (5, 3, 2), 0.5)),
+    Case((0, 1, 3, 2, 0), "circle", 12, 12, s=0.8),          # one workgroup per CU
+    Case((1, 1, 2, 2, 0), "circle", 7, 18, s=1.1, mixed=(7, 18, (18, 9, 4), 1.1)),
+    Case((1, 1, 2, 3, 0), "circle", 3, 41),
+    Case((1, 1, 2, 3, 2), "circle", 4, 31),
+    Case((1, 1, 3, 2, 0), "circle", 6, 22, s=1.35),
+    Case((1, 1, 3, 3, 0), "circle", 4, 32),
+    # 8 vehicles at Hp 30 with a horizon array run this kernel, not the compiled c3 one
+    Case((1, 1, 4, 2, 0), "circle", 4, 48, mixed=(8, 30, (30, 15, 6), 1.0)),
+    Case((1, 1, 4, 3, 0), "circle", 7, 28, s=1.15),           # its only obstacle-free shape
+)
+NEW_CASES = tuple(c for c in CASES if c.covered_by is None)
+MIXED_CASES = tuple(c for c in CASES if c.mixed is not None)
+# Reachable instantiations whose case faulted on the GPU with the cause not found: listed
+# here (and in DESIGN.md) instead of tested, so the reachability test names them.
+REACHABLE_UNTESTED_FAULTED = ()
+
+
+def by_id(cid):
+    return next(c for c in CASES if c.id == cid)
+
+
+def _paths():
+    here = os.path.dirname(os.path.abspath(__file__))
+    root = os.path.dirname(here)
+    for p in (here, root, os.path.join(root, "senquential-convex-programming-for-trajectory-planning_amd")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+
+
+def scenario(kind, n_veh, hp):
+    _paths()
+    from oracle import scp_reference as R
+    if kind == "frog":
+        return R.frog_scenario(Hp=hp)
+    return R.circle_scenario(n_veh, Hp=hp)
+
+
+def make_inputs(kind, n_veh, hp_max, s=1.0, hps=None):
+    """(scenario, batch) of a row: N_PROBLEMS problems, starts scaled by ``s``."""
+    _paths()
+    from scpqp import batch as BT
+    sc = scenario(kind, n_veh, hp_max)
+    bt = BT.make_batch(sc, N_PROBLEMS, base_seed=BASE_SEED, mixed_hp=hps)
+    assert bt.hp_max == hp_max
+    bt.x0[:, :, 0:2] *= s
+    return sc, bt
+
+
+def case_inputs(case):
+    return make_inputs(case.scenario, case.n_veh, case.hp_max, case.s, case.hps)
+
+
+def mixed_inputs(case):
+    n_veh, hp_max, hps, s = case.mixed
+    return make_inputs(case.scenario, n_veh, hp_max, s, hps)
+
+
+def problem_obst(sc, bt, b):
+    H = int(bt.hp[b])
+    return bt.obst[b].reshape(-1)[:sc.nObst * 2 * H].reshape(sc.nObst, 2, H)
+
+
+def oracle_jobs(kind, n_veh, sc, bt):
+    return [(kind, n_veh, bt.hp_max, int(bt.hp[b]), bt.x0[b], bt.u0[b], bt.ec_noise[b],
+             problem_obst(sc, bt, b)) for b in range(bt.size)]
+
+
+def oracle_job(args):
+    """One problem on the oracle, for a spawn pool: the full SCP solve with its history, and
+    the single-QP solve in both polish modes.  Returns (SCPResult, u of the one-QP run,
+    active collision rows of the last QP, the two modes' distance on the one-QP u); the
+    history's row matrices are dropped once the active rows are counted
+    (a 12-vehicle history is ~1 MB per iteration to pickle otherwise)."""
+    _paths()
+    from oracle import scp_reference as R
+    import scp_parity as SP
+    SP.single_thread_blas()
+    kind, n_veh, hp_max, hp, x0, u0, ec, obst = args
+    sc = scenario(kind, n_veh, hp_max)
+    p = R.make_problem(sc, x0, u0, ec, Hp=hp, obst=obst if sc.nObst else None)
+    r = R.scp_solve(p, mode="structured", keep_history=True)
+    one = R.scp_solve(p, mode="structured", max_scp=1)
+    reg = R.scp_solve(p, mode="structured", max_scp=1, polish="regularised")
+    spread = float(np.max(np.abs(one.u - reg.u)))
+    last = r.history[-1]
+    active = int(np.sum(np.abs(last["b"] - last["A"] @ last["z"]) < ACTIVE_TOL))
+    assert all(h["certified"] for h in r.history)
+    for h in r.history:
+        del h["A"], h["b"], h["u_lin"]
+    r.lin = None
+    return r, one.u, active, spread

@@ -33,6 +33,7 @@ def test_header_declares_the_boundary():
     assert fns == sorted(["scpqp_create", "scpqp_destroy", "scpqp_last_error", "scpqp_version",
                           "scpqp_solve", "scpqp_linearize", "scpqp_evaluate",
                           "scpqp_sample_reference", "scpqp_resources", "scpqp_trace_layout",
+                          "scpqp_plan_query",
                           "scpqp_delay_compensate", "scpqp_plant_step", "scpqp_clip_controls"])
     assert sorted(LB.EXPORTS) == fns
 
@@ -97,7 +98,7 @@ PROBE = r"""
 #define O(t, f) printf(#t "." #f " %zu\n", offsetof(t, f));
 int main(void) {
   S(scpqp_dims) S(scpqp_params) S(scpqp_batch_in) S(scpqp_batch_out) S(scpqp_lin_out) S(scpqp_eval_out)
-  S(scpqp_plant_params)
+  S(scpqp_plant_params) S(scpqp_plan_info)
   %s
   return 0;
 }
@@ -107,7 +108,8 @@ int main(void) {
 def test_ctypes_layout_matches_header(tmp_path):
     structs = {"scpqp_dims": LB.Dims, "scpqp_params": LB.Params, "scpqp_batch_in": LB.BatchIn,
                "scpqp_batch_out": LB.BatchOut, "scpqp_lin_out": LB.LinOut,
-               "scpqp_eval_out": LB.EvalOut, "scpqp_plant_params": LB.PlantParams}
+               "scpqp_eval_out": LB.EvalOut, "scpqp_plant_params": LB.PlantParams,
+               "scpqp_plan_info": LB.PlanInfo}
     offs = "".join(f"O({cn}, {f}) " for cn, cls in structs.items() for f, _ in cls._fields_)
     src = tmp_path / "probe.c"
     src.write_text(PROBE.replace("%s", offs))

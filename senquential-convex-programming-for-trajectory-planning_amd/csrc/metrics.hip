@@ -32,12 +32,19 @@
 // have 1 and 5 vehicles, and the chunking stays that of the constant obstacles, so the
 // nominal rows give bitwise what those give.  The instantiation without kRows is the
 // kernel the other entry points have always launched.
+//
+// scpqp_metrics_accumulate_posed (include/scpqp_manoeuvres.h) is the third instantiation,
+// kPosed: obstacle o of realisation b at tick k is read from the dense poses
+// pose[b][o][k][0..2] the caller computed (scpqp_manoeuvres_pose), and sized by its row.  The
+// poses stay in global memory (each is read n_veh times, from L2), so the chunking is again
+// that of the constant obstacles; the item costs one sincos of the heading.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 
 #include <vector>
 
+#include "scpqp_manoeuvres.h"
 #include "scpqp_metrics.h"
 #include "scpqp_obstacle_pose.h"
 #include "scpqp_obstacles.h"
@@ -144,16 +151,34 @@ __device__ __forceinline__ double wave_min(double x) {
     return x;
 }
 
+// where the obstacles of a realisation come from
+enum ObstSrc { kConst = 0, kRowsSrc = 1, kPosed = 2 };
+
+// the arguments of the source: the rows (kRows, kPosed; not read otherwise) and, for kPosed
+// alone, the dense poses, so that the two other instantiations keep their argument list
+template <int kSrc>
+struct SrcArgs {
+    const double* rows;
+};
+template <>
+struct SrcArgs<kPosed> {
+    const double* rows;
+    const double* pose;
+};
+
 // kRows: obstacle o of realisation b is rows[b][o] (include/scpqp_obstacles.h) instead of
-// the constants' P->obst[o]; rows is not read otherwise
-template <bool kRows>
+// the constants' P->obst[o]; kPosed: it is at src.pose[b][o][k] with the row's extents
+// (include/scpqp_manoeuvres.h)
+template <int kSrc>
 __global__ __launch_bounds__(WAVE) void metrics_kernel(const DevConst* __restrict__ table, int n_var,
                                                        const int* __restrict__ variant, int n_ticks,
                                                        int tick0, int k_first,
                                                        const double* __restrict__ x_path,
                                                        scpqp_metrics_acc acc, bool have_acc,
                                                        scpqp_metrics_dense dense,
-                                                       const double* __restrict__ rows) {
+                                                       const SrcArgs<kSrc> src) {
+    constexpr bool kRows = kSrc == kRowsSrc;
+    const double* __restrict__ rows = src.rows;
     __shared__ double pose[ENT_CAP][4];     // x, y, cos h, sin h of entry (tick, vehicle)
     __shared__ double xt[ENT_CAP];          // its cross-track error
     __shared__ int coll[ENT_CAP];           // per tick of the chunk: any gap of 0
@@ -170,7 +195,8 @@ __global__ __launch_bounds__(WAVE) void metrics_kernel(const DevConst* __restric
     const int nVO = nV * nO;
     const int chunk = ENT_CAP / nV;         // ticks per chunk (>= 42)
     const double* xb = x_path + b * nV * K * NX;
-    const double* rb = nullptr;             // kRows: the realisation's rows [nO][7]
+    const double* rb = nullptr;             // kRows, kPosed: the realisation's rows [nO][7]
+    const double* posed = nullptr;          // kPosed: its poses [nO][K][3]
 
     if constexpr (kRows) {
         // a bad row leaves the realisation untouched, like a bad variant index: the lanes
@@ -178,6 +204,14 @@ __global__ __launch_bounds__(WAVE) void metrics_kernel(const DevConst* __restric
         rb = rows + b * nO * SCPQP_OBST_NP;
         bool bad = false;
         for (int o = lane; o < nO; o += WAVE) bad |= scpqp_obst_dev::bad_row(rb + o * SCPQP_OBST_NP);
+        if (__any(bad)) return;
+    } else if constexpr (kSrc == kPosed) {
+        // likewise a bad row or a pose entry that is not finite (a bad lane's block is NaN)
+        rb = rows + b * nO * SCPQP_OBST_NP;
+        posed = src.pose + b * nO * K * 3;
+        bool bad = false;
+        for (int o = lane; o < nO; o += WAVE) bad |= scpqp_obst_dev::bad_row(rb + o * SCPQP_OBST_NP);
+        for (int e = lane; e < nO * K * 3; e += WAVE) bad |= !isfinite(posed[e]);
         if (__any(bad)) return;
     } else {
         for (int o = lane; o < nO; o += WAVE) sincos(P->obst[o][2], &ocs[o][1], &ocs[o][0]);
@@ -239,6 +273,12 @@ __global__ __launch_bounds__(WAVE) void metrics_kernel(const DevConst* __restric
                 const double* ob = rb + o * SCPQP_OBST_NP;
                 const scpqp_obst_dev::Pose q = scpqp_obst_dev::pose_at(ob, t);
                 O = Rect{q.x, q.y, q.c, q.s, ob[SCPQP_OBST_LENGTH] * 0.5, ob[SCPQP_OBST_WIDTH] * 0.5};
+            } else if constexpr (kSrc == kPosed) {
+                const double* ob = rb + o * SCPQP_OBST_NP;
+                const double* q = posed + ((size_t)o * K + k) * 3;
+                double s, c;
+                sincos(q[2], &s, &c);
+                O = Rect{q[0], q[1], c, s, ob[SCPQP_OBST_LENGTH] * 0.5, ob[SCPQP_OBST_WIDTH] * 0.5};
             } else {
                 const double* ob = P->obst[o];
                 O = Rect{t * ob[3] * ocs[o][0] + ob[0], t * ob[3] * ocs[o][1] + ob[1], ocs[o][0],
@@ -409,6 +449,11 @@ int accumulate(scpqp_metrics* m, int32_t B, int32_t n_ticks, int32_t tick0, int3
                const double* x_path, const scpqp_metrics_acc* acc, const scpqp_metrics_dense* dense,
                const int32_t* variant, bool with_rows, const double* rows, void* stream);
 
+int accumulate_from(scpqp_metrics* m, int32_t B, int32_t n_ticks, int32_t tick0, int32_t k_first,
+                    const double* x_path, const scpqp_metrics_acc* acc,
+                    const scpqp_metrics_dense* dense, const int32_t* variant, int src,
+                    const double* rows, const double* pose, void* stream);
+
 }  // namespace
 
 extern "C" {
@@ -516,15 +561,36 @@ int scpqp_metrics_accumulate_obstacles(scpqp_metrics* m, int32_t B, int32_t n_ti
                       stream);
 }
 
+int scpqp_metrics_accumulate_posed(scpqp_metrics* m, int32_t B, int32_t n_ticks, int32_t tick0,
+                                   int32_t k_first, const double* x_path,
+                                   const scpqp_metrics_acc* acc, const scpqp_metrics_dense* dense,
+                                   const int32_t* variant, const double* rows, const double* pose,
+                                   void* stream) {
+    return accumulate_from(m, B, n_ticks, tick0, k_first, x_path, acc, dense, variant, kPosed, rows,
+                           pose, stream);
+}
+
 }  // extern "C"
 
 namespace {
 
-// the one body of the three accumulate entry points; with_rows: the obstacle rows of
-// include/scpqp_obstacles.h pose the obstacles (rows non-NULL once there is work)
+// the body of the accumulate entry points of scpqp_metrics.h, scpqp_variants.h and
+// scpqp_obstacles.h; with_rows: the obstacle rows of include/scpqp_obstacles.h pose the
+// obstacles (rows non-NULL once there is work)
 int accumulate(scpqp_metrics* m, int32_t B, int32_t n_ticks, int32_t tick0, int32_t k_first,
                const double* x_path, const scpqp_metrics_acc* acc, const scpqp_metrics_dense* dense,
                const int32_t* variant, bool with_rows, const double* rows, void* stream) {
+    return accumulate_from(m, B, n_ticks, tick0, k_first, x_path, acc, dense, variant,
+                           with_rows ? kRowsSrc : kConst, rows, nullptr, stream);
+}
+
+// src: where the obstacles come from (ObstSrc); kPosed reads the rows' extents and the dense
+// poses [B][n_obst][n_ticks + 1][3] of include/scpqp_manoeuvres.h
+int accumulate_from(scpqp_metrics* m, int32_t B, int32_t n_ticks, int32_t tick0, int32_t k_first,
+                    const double* x_path, const scpqp_metrics_acc* acc,
+                    const scpqp_metrics_dense* dense, const int32_t* variant, int src,
+                    const double* rows, const double* pose, void* stream) {
+    const bool with_rows = src != kConst;
     if (B < 0 || n_ticks < 0) return scpqp_fail_(SCPQP_E_ARG, "batch size / n_ticks < 0");
     if (tick0 < 0) return scpqp_fail_(SCPQP_E_ARG, "tick0 < 0");
     if (k_first != 0 && k_first != 1) return scpqp_fail_(SCPQP_E_ARG, "k_first must be 0 or 1");
@@ -536,6 +602,9 @@ int accumulate(scpqp_metrics* m, int32_t B, int32_t n_ticks, int32_t tick0, int3
         return scpqp_fail_(SCPQP_E_ARG, "obstacle rows on a handle without obstacles");
     if (with_rows && (long long)B * m->n_obst * SCPQP_OBST_NP > 0x7fffffffLL)
         return scpqp_fail_(SCPQP_E_SIZE, "B * n_obst too large");
+    if (src == kPosed && (K > 0x7fffffffLL / 3 / m->n_obst ||
+                          (long long)B * m->n_obst * K * 3 > 0x7fffffffLL))
+        return scpqp_fail_(SCPQP_E_SIZE, "B * n_obst * (n_ticks + 1) * 3 too large");
     const long long per_tick = (long long)m->n_veh * NX > (long long)m->n_veh * m->n_obst
                                    ? (long long)m->n_veh * NX : (long long)m->n_veh * m->n_obst;
     const long long widest = per_tick > m->n_pair ? per_tick : m->n_pair;
@@ -547,20 +616,25 @@ int accumulate(scpqp_metrics* m, int32_t B, int32_t n_ticks, int32_t tick0, int3
     if (B == 0) return 0;
     if (!x_path) return scpqp_fail_(SCPQP_E_ARG, "null array");
     if (with_rows && !rows) return scpqp_fail_(SCPQP_E_ARG, "null rows array");
+    if (src == kPosed && !pose) return scpqp_fail_(SCPQP_E_ARG, "null pose array");
     if (acc)
         if (int rc = check_acc(acc)) return rc;
     hipError_t e = hipSetDevice(m->device);
     if (e != hipSuccess) return scpqp_fail_(SCPQP_E_HIP, hipGetErrorString(e));
     const scpqp_metrics_acc a = acc ? *acc : scpqp_metrics_acc{};
     const scpqp_metrics_dense d = dense ? *dense : scpqp_metrics_dense{};
-    if (with_rows)
-        hipLaunchKernelGGL(metrics_kernel<true>, dim3((unsigned)B), dim3(WAVE), 0,
+    if (src == kPosed)
+        hipLaunchKernelGGL(metrics_kernel<kPosed>, dim3((unsigned)B), dim3(WAVE), 0,
                            static_cast<hipStream_t>(stream), m->dev, m->n_var, variant, n_ticks,
-                           tick0, k_first, x_path, a, acc != nullptr, d, rows);
+                           tick0, k_first, x_path, a, acc != nullptr, d, SrcArgs<kPosed>{rows, pose});
+    else if (src == kRowsSrc)
+        hipLaunchKernelGGL(metrics_kernel<kRowsSrc>, dim3((unsigned)B), dim3(WAVE), 0,
+                           static_cast<hipStream_t>(stream), m->dev, m->n_var, variant, n_ticks,
+                           tick0, k_first, x_path, a, acc != nullptr, d, SrcArgs<kRowsSrc>{rows});
     else
-        hipLaunchKernelGGL(metrics_kernel<false>, dim3((unsigned)B), dim3(WAVE), 0,
+        hipLaunchKernelGGL(metrics_kernel<kConst>, dim3((unsigned)B), dim3(WAVE), 0,
                            static_cast<hipStream_t>(stream), m->dev, m->n_var, variant, n_ticks,
-                           tick0, k_first, x_path, a, acc != nullptr, d, nullptr);
+                           tick0, k_first, x_path, a, acc != nullptr, d, SrcArgs<kConst>{nullptr});
     return launched();
 }
 

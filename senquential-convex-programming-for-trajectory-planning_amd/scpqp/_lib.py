@@ -1,7 +1,7 @@
 """ctypes binding of ``include/scpqp.h``, ``include/scpqp_noise.h``,
 ``include/scpqp_metrics.h``, ``include/scpqp_variants.h``, ``include/scpqp_truth.h``,
-``include/scpqp_obstacles.h``, ``include/scpqp_sensing.h``, ``include/scpqp_estimator.h`` and
-``include/scpqp_tracker.h`` (the C-ABI of the HIP library).
+``include/scpqp_obstacles.h``, ``include/scpqp_sensing.h``, ``include/scpqp_estimator.h``,
+``include/scpqp_tracker.h`` and ``include/scpqp_manoeuvres.h`` (the C-ABI of the HIP library).
 
 The shared library ``libscpqp.so`` is built in-tree (``__graft_entry__.build()``
 or ``python -m scpqp.build``).  There is no CPU fallback: if the library or a
@@ -230,6 +230,26 @@ TRK_DSINC_SWITCH = 0.02
 # every symbol include/scpqp_tracker.h declares (checked by tests/test_tracker_host.py)
 TRK_EXPORTS = ("scpqp_obstacles_track",)
 
+MAN_NSEG = 4
+MAN_NF = 3
+MAN_DUR, MAN_ACCEL, MAN_DYAW = range(MAN_NF)
+MAN_FIELDS = ("dur", "accel", "dyaw")
+MAN_PR_SWITCH = 0.1
+NOISE_SITE_MANOEUVRE = 8
+
+
+class ManoeuvreDist(C.Structure):
+    """scpqp_manoeuvres_dist (include/scpqp_manoeuvres.h)."""
+    _fields_ = [("n_obst", C.c_int32), ("pad0", C.c_int32),
+                ("mean", (C.c_double * MAN_NF) * MAN_NSEG),
+                ("field", (TruthField * MAN_NF) * MAN_NSEG),
+                ("seed", C.c_uint64), ("b_offset", C.c_uint32), ("pad1", C.c_uint32)]
+
+
+# every symbol include/scpqp_manoeuvres.h declares (checked by tests/test_manoeuvres_host.py)
+MAN_EXPORTS = ("scpqp_manoeuvres_state", "scpqp_manoeuvres_pose", "scpqp_manoeuvres_sample",
+               "scpqp_metrics_accumulate_posed")
+
 _lib = None
 
 
@@ -355,6 +375,17 @@ def load(path=None):
         SS = C.POINTER(SenseStream)
         lib.scpqp_obstacles_track.argtypes = [I, I, I, V, V, SS, V, D, D, D, D, V, V, V, V, V, V]
         lib.scpqp_obstacles_track.restype = C.c_int
+    # likewise an A/B build from before the obstacle manoeuvres
+    if path is None or hasattr(lib, "scpqp_manoeuvres_state"):
+        D, I = C.c_double, C.c_int32
+        lib.scpqp_manoeuvres_state.argtypes = [I, I, V, V, D, V, V]
+        lib.scpqp_manoeuvres_state.restype = C.c_int
+        lib.scpqp_manoeuvres_pose.argtypes = [I, I, V, V, D, I, I, V, V]
+        lib.scpqp_manoeuvres_pose.restype = C.c_int
+        lib.scpqp_manoeuvres_sample.argtypes = [C.POINTER(ManoeuvreDist), I, V, V]
+        lib.scpqp_manoeuvres_sample.restype = C.c_int
+        lib.scpqp_metrics_accumulate_posed.argtypes = [H, I, I, I, I, V, MA, MD, V, V, V, V]
+        lib.scpqp_metrics_accumulate_posed.restype = C.c_int
     if path is None:
         _lib = lib
     return lib

@@ -2,7 +2,7 @@
 
 The library is linked from separate translation units compiled in parallel:
 ``scpqp.hip`` (the C-ABI host side), ``plant.hip``, ``metrics.hip``, ``obstacles.hip``,
-``sensing.hip``, ``estimator.hip``, ``tracker.hip``, and ``kernels.hip`` once per kernel
+``sensing.hip``, ``estimator.hip``, ``tracker.hip``, ``manoeuvres.hip``, and ``kernels.hip`` once per kernel
 group (``-DSCPQP_KGROUP=1..10``: the kernel instantiations of ``scpqp_kernel.h``).
 """
 from __future__ import annotations
@@ -23,7 +23,8 @@ KERNEL_SRC = os.path.join(CSRC, "kernels.hip")
 HEADER = os.path.join(CSRC, "scpqp_kernel.h")
 SRCS = [SRC, os.path.join(CSRC, "plant.hip"), os.path.join(CSRC, "metrics.hip"),
         os.path.join(CSRC, "obstacles.hip"), os.path.join(CSRC, "sensing.hip"),
-        os.path.join(CSRC, "estimator.hip"), os.path.join(CSRC, "tracker.hip")]
+        os.path.join(CSRC, "estimator.hip"), os.path.join(CSRC, "tracker.hip"),
+        os.path.join(CSRC, "manoeuvres.hip")]
 KERNEL_GROUPS = 10
 INCLUDE = os.path.join(_REPO, "include")
 LIB_PATH = os.path.join(_PKG, "libscpqp.so")
@@ -51,7 +52,9 @@ def build_library(force=False, verbose=False, defines=(), out=None, csrc=None):
     hdr = os.path.join(src_dir, os.path.basename(HEADER))
     deps = srcs + [ksrc, hdr, os.path.join(src_dir, "scpqp_philox.h"),
                    os.path.join(src_dir, "scpqp_obstacle_pose.h"),
+                   os.path.join(src_dir, "scpqp_manoeuvre_pose.h"),
                    os.path.join(src_dir, "scpqp_bicycle.h"),
+                   os.path.join(INCLUDE, "scpqp_manoeuvres.h"),
                    os.path.join(INCLUDE, "scpqp_obstacles.h"),
                    os.path.join(INCLUDE, "scpqp_sensing.h"),
                    os.path.join(INCLUDE, "scpqp_estimator.h"),

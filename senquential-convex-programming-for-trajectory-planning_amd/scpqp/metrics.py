@@ -83,6 +83,7 @@ class PathMetrics:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.nV, self.nO = int(scenario.nVeh), int(scenario.nObst)
         self.n_pair = self.nV * (self.nV - 1) // 2
+        self.tick_length = float(scenario.tick_length)
         self.max_batch = int(max_batch)
         if self.max_batch < 1:
             raise ValueError("max_batch must be >= 1")
@@ -133,7 +134,8 @@ class PathMetrics:
         LB.check(self.lib.scpqp_metrics_reset(self.h, B, C.byref(self._acc), self._stream()),
                  self.lib)
 
-    def accumulate(self, x_path, tick0, k_first, dense=False, variant=None, obstacles=None):
+    def accumulate(self, x_path, tick0, k_first, dense=False, variant=None, obstacles=None,
+                   manoeuvres=None, check_off=True):
         """Merge one step's path ``x_path`` [B, nVeh, K, 6] (a float64 device tensor, the
         output of ``plant.plant_step``; entry k is global tick ``tick0 + k``) over its
         entries ``k_first..K-1``.  ``dense=True`` also returns this call's ``gap_veh``
@@ -144,7 +146,16 @@ class PathMetrics:
         realisation's accumulator and dense rows are left as they are.
         ``obstacles`` [B, nObst, 7] (scpqp/obstacles.py; include/scpqp_obstacles.h): obstacle
         o of realisation b moves and is sized by its own row instead of the scenario's
-        constant obstacle; a realisation with a bad row is left as it is."""
+        constant obstacle; a realisation with a bad row is left as it is.
+        ``manoeuvres`` [B, nObst, 4, 3] (scpqp/manoeuvres.py; include/scpqp_manoeuvres.h), with
+        ``obstacles=``: the obstacles follow their schedules.  Their poses at the call's ticks
+        are computed first (``manoeuvres.pose``) and the gaps are measured against them
+        (scpqp_metrics_accumulate_posed); a realisation with a bad lane is left as it is.
+        ``check_off`` (default True): the schedule is first checked on the host
+        (``manoeuvres.is_off``: one device-to-host copy and a synchronisation), and one in which
+        no piece does anything takes the ``obstacles=`` path.  ``check_off=False`` skips the
+        check and sends the schedule through the posed entry as it is: for a caller that has
+        already made the check (the rollout makes it once, at reset)."""
         if x_path.dtype != torch.float64 or x_path.device != self.device or x_path.dim() != 4:
             raise ValueError("x_path must be a float64 [B, nVeh, K, 6] tensor on the metrics' device")
         B, V, K, nx = (int(s) for s in x_path.shape)
@@ -168,6 +179,18 @@ class PathMetrics:
                                 gap_obs=out["gap_obs"].data_ptr() if self.nO else None,
                                 xtrack=out["xtrack"].data_ptr())
         acc = None if dense == "only" else C.byref(self._acc)
+        if manoeuvres is not None and obstacles is None:
+            raise ValueError("manoeuvres needs obstacles= rows")
+        posed = None
+        if manoeuvres is not None:
+            from . import manoeuvres as MAN
+            if not isinstance(manoeuvres, torch.Tensor) or manoeuvres.dtype != torch.float64 \
+                    or manoeuvres.device != self.device \
+                    or tuple(manoeuvres.shape) != (B, self.nO, MAN.NSEG, MAN.NF):
+                raise ValueError(f"manoeuvres must be a float64 [B, nObst, 4, 3] = [{B}, {self.nO}, "
+                                 f"4, 3] tensor on the metrics' device")
+            if not check_off or not MAN.is_off(manoeuvres):
+                posed = manoeuvres.contiguous()
         if obstacles is not None:
             rows = obstacles
             if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float64 \
@@ -179,6 +202,16 @@ class PathMetrics:
                 raise ValueError(f"obstacles must be [B, nObst, 7] = [{B}, {self.nO}, 7], got "
                                  f"{list(rows.shape)}")
             rows = rows.contiguous()
+            if posed is not None:
+                p = MAN.pose(rows, posed, self.tick_length, int(tick0), K - 1)
+                LB.check(self.lib.scpqp_metrics_accumulate_posed(
+                    self.h, B, K - 1, int(tick0), int(k_first), C.c_void_p(x.data_ptr()), acc,
+                    None if D is None else C.byref(D),
+                    None if var is None else C.c_void_p(var.data_ptr()),
+                    C.c_void_p(rows.data_ptr()), C.c_void_p(p.data_ptr()), self._stream()),
+                    self.lib)
+                self._last_variant, self._last_rows, self._last_pose = var, rows, p
+                return out
             LB.check(self.lib.scpqp_metrics_accumulate_obstacles(
                 self.h, B, K - 1, int(tick0), int(k_first), C.c_void_p(x.data_ptr()), acc,
                 None if D is None else C.byref(D),

@@ -35,6 +35,9 @@ and the obstacles noisy, biased, late or lost (include/scpqp_sensing.h).
 that measurement and the delay compensation (include/scpqp_estimator.h).
 ``reset(..., tracker=)`` puts one per (realisation, obstacle) between the obstacle measurement
 and the obstacle prediction (include/scpqp_tracker.h).
+``reset(..., manoeuvres=)`` makes the obstacles brake, accelerate and turn in pieces on top of
+their rows (include/scpqp_manoeuvres.h); the controller measures them as before and knows
+nothing of the schedule.
 """
 from __future__ import annotations
 
@@ -193,6 +196,7 @@ class ClosedLoopBatch:
         self.x_held = None
         self.est_rows = None           # the estimator tuning of reset(..., estimator=)
         self.trk_rows = None           # the tracker tuning of reset(..., tracker=)
+        self.man_rows = None           # the manoeuvre schedule of reset(..., manoeuvres=)
         self.trace = trace     # keep every step's solve inputs and per-SCP-iteration trace
         self.out = self.solver.alloc_out(self.B, trace=trace)
         self.history = []
@@ -204,7 +208,7 @@ class ClosedLoopBatch:
 
     def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0, truth=None,
               obstacles=None, sensing=None, obstacle_sensing=None, sense_seed=None,
-              estimator=None, tracker=None):
+              estimator=None, tracker=None, manoeuvres=None):
         """main.py:73-75: vehiclePathFullRes[:, v, 0] = x0; the control path holds
         scenario.u0 for the first ticks_delay_u + ticks_per_sim + 1 ticks.
 
@@ -254,7 +258,30 @@ class ClosedLoopBatch:
         the estimate replaces the straight extrapolation as the solve's ``obst``.  It needs
         ``obstacles=`` rows.  The world (metrics, plotted paths) keeps the true rows.
         Validated here, before anything is launched; None: nothing is allocated or launched
-        and the prediction is what it was."""
+        and the prediction is what it was.
+
+        ``manoeuvres`` [B, nObst, 4, 3] (scpqp/manoeuvres.py; include/scpqp_manoeuvres.h): every
+        (realisation, obstacle) accelerates and turns in up to four pieces on top of its row.
+        It needs ``obstacles=`` rows.  The controller measures the true pose and the true
+        current speed at the measurement tick (the snapshot row, recorded as ``obst_state``)
+        and predicts from them as before: exact, sensed or tracked.  The metrics and
+        ``result_for_plot`` follow the schedule.  Validated here, before anything is launched;
+        None, or a schedule in which no piece does anything: nothing is allocated or launched
+        and the rollout is what it was."""
+        if manoeuvres is not None:
+            from . import manoeuvres as MAN
+            if obstacles is None:
+                raise ValueError("manoeuvres needs obstacles= rows: pass "
+                                 "obstacles.nominal(scenario, B) for the scenario's own")
+            mn = manoeuvres.detach().cpu().numpy() if isinstance(manoeuvres, torch.Tensor) \
+                else np.asarray(manoeuvres, float)
+            if tuple(mn.shape) != (self.B, self.nO, MAN.NSEG, MAN.NF):
+                raise ValueError(f"manoeuvres must be [B, nObst, 4, 3] = [{self.B}, {self.nO}, 4, 3]")
+            ob = obstacles.detach().cpu().numpy() if isinstance(obstacles, torch.Tensor) \
+                else np.asarray(obstacles, float)
+            MAN.validate(mn, ob if tuple(ob.shape) == (self.B, self.nO, 7) else None)
+            if MAN.is_off(mn):
+                manoeuvres = None
         if tracker is not None:
             from . import tracker as TRK
             if obstacles is None:
@@ -359,6 +386,9 @@ class ClosedLoopBatch:
             self.trk_x, self.trk_cov = TRK.alloc(self.B, self.nO, self.device)
         self.trk_tick = None           # the global tick of the previous obstacle measurement
         self.trk_rec = None            # this step's (estimate, nis, measurement)
+        self.man_rows = None if manoeuvres is None else torch.as_tensor(
+            manoeuvres, dtype=torch.float64, device=self.device).contiguous().clone()
+        self.obst_state = None         # this step's snapshot rows
         self.last_path = None
         self.u_prev = None
         self.history = []
@@ -377,14 +407,20 @@ class ClosedLoopBatch:
             # straight, per (realisation, obstacle) on the device
             from . import obstacles as OB
             sc = self.sc
+            rows, t_meas = self.obst_rows, tick_meas * sc.tick_length
+            if self.man_rows is not None:
+                # the obstacle manoeuvres: the true pose and current speed at the measurement
+                # tick as a row; measured at its own t = 0 it is that pose exactly
+                from . import manoeuvres as MAN
+                rows, t_meas = MAN.state(self.obst_rows, self.man_rows, t_meas), 0.0
+                self.obst_state = rows
             if self.trk_rows is not None:
                 # the obstacle tracker (include/scpqp_tracker.h): the same measurement,
                 # filtered over the time since the previous one, predicted on its arc
                 from . import tracker as TRK
                 g0 = tick_meas if self.trk_tick is None else self.trk_tick
-                obst, z, nis = TRK.step(self.obst_rows, self.osense_rows, self.sense_seed, self.i,
-                                        self.sense_offset, self.trk_rows,
-                                        tick_meas * sc.tick_length,
+                obst, z, nis = TRK.step(rows, self.osense_rows, self.sense_seed, self.i,
+                                        self.sense_offset, self.trk_rows, t_meas,
                                         (tick_meas - g0) * sc.tick_length,
                                         sc.delay_x + sc.dt + sc.delay_u, sc.dt, self.Hp,
                                         self.trk_x, self.trk_cov)
@@ -394,11 +430,10 @@ class ClosedLoopBatch:
             if self.osense_rows is not None:
                 # the sensing truth: the same extrapolation from a noisy pose and speed
                 from . import sensing as SE
-                return SE.predict_sensed(self.obst_rows, self.osense_rows, self.sense_seed, self.i,
-                                         self.sense_offset, tick_meas * sc.tick_length,
+                return SE.predict_sensed(rows, self.osense_rows, self.sense_seed, self.i,
+                                         self.sense_offset, t_meas,
                                          sc.delay_x + sc.dt + sc.delay_u, sc.dt, self.Hp)
-            return OB.predict(self.obst_rows, tick_meas * sc.tick_length,
-                              sc.delay_x + sc.dt + sc.delay_u, sc.dt, self.Hp)
+            return OB.predict(rows, t_meas, sc.delay_x + sc.dt + sc.delay_u, sc.dt, self.Hp)
         if self.var_obstacles is not None:
             # one prediction per variant on the host, gathered per realisation on the device
             fut = np.stack([self._predict(ob, tick_meas) for ob in self.var_obstacles])
@@ -503,7 +538,8 @@ class ClosedLoopBatch:
         if self.path_metrics is not None:
             # every global tick once: entry 0 of a later step is the previous step's last
             self.path_metrics.accumulate(path, tick0=i * tps, k_first=0 if i == 0 else 1,
-                                         variant=self.variant_of, obstacles=self.obst_rows)
+                                         variant=self.variant_of, obstacles=self.obst_rows,
+                                         manoeuvres=self.man_rows, check_off=False)
         self.last_path = path
         self.state = path[:, :, tps, :].contiguous()
         rec = dict(x0=x0, u0=u_hold, umax=umax, U=U, traj=out.traj.clone(),
@@ -513,6 +549,8 @@ class ClosedLoopBatch:
             rec["epoch"] = i
         if self.obst_rows is not None:
             rec["obst"] = obst      # what the controller was told of the obstacle truth
+        if self.man_rows is not None:
+            rec["obst_state"] = self.obst_state   # the manoeuvring obstacles at the measurement tick
         if self.trk_rows is not None:
             # the tracker's estimate, its innovations and the obstacle measurement it took
             rec["obst_est"], rec["obst_nis"], rec["obst_meas"] = self.trk_rec
@@ -576,7 +614,13 @@ class ClosedLoopBatch:
         if self.obst_rows is not None:
             # the realisation's own obstacle motion (include/scpqp_obstacles.h)
             from . import obstacles as OB
-            p = OB.pose(self.obst_rows[b:b + 1], sc.tick_length, 0, T)[0].cpu().numpy()
+            if self.man_rows is not None:
+                # and its manoeuvres (include/scpqp_manoeuvres.h)
+                from . import manoeuvres as MAN
+                p = MAN.pose(self.obst_rows[b:b + 1], self.man_rows[b:b + 1], sc.tick_length, 0,
+                             T)[0].cpu().numpy()
+            else:
+                p = OB.pose(self.obst_rows[b:b + 1], sc.tick_length, 0, T)[0].cpu().numpy()
             obs[:, 0], obs[:, 1] = p[:, :, 0], p[:, :, 1]
         elif self.nO:
             t = np.arange(T + 1) * sc.tick_length                       # main.py:61-71

@@ -16,6 +16,7 @@ realisation per spawned single-threaded worker.
                                    [--estimate [--est-q-pos Q] [--est-q-heading Q]
                                     [--est-q-speed Q] [--est-q-steer Q]]]
                                   [--track]
+                                  [--obstacle-brake DECEL | --obstacle-weave DYAW]
 
 Prints one JSON line: realisation-steps/s on the GPU and the CPU, and the
 largest state difference between the two on the CPU sample.  ``--noise-seed S``
@@ -63,6 +64,14 @@ the batch is then (``--sense-pos``, ``--sense-heading``, 0) per obstacle, exact 
 reports the timed, tracked run (``metrics``, ``gpu_ms_per_step``, ``mean_nis_obst``) next to the
 same batch and obstacle sensor without the tracker, run and timed after it
 (``metrics_untracked``, ``gpu_ms_per_step_untracked``, ``mean_scp_iters_untracked``).
+``--obstacle-brake DECEL`` gives every (realisation, obstacle) a manoeuvre schedule
+(include/scpqp_manoeuvres.h): it coasts until a start time uniform over the rollout, then brakes
+at DECEL m/s^2 until it stands.  ``--obstacle-weave DYAW`` gives it a lane change at such a start
+time instead: DYAW rad/s more for WEAVE_SECONDS, then DYAW less for as long.  Both draw through
+``ManoeuvreDist`` from ``--obstacle-seed`` and run in every run of the tool, the comparison runs
+included.  Without ``--obstacle-yaw`` the rows are the scenario's own (``--obstacle-yaw 0``);
+``--track`` is accepted with either.  They imply ``--metrics``; the CPU sample keeps the straight
+obstacles.
 """
 import json
 import multiprocessing as mp
@@ -77,6 +86,8 @@ import numpy as np  # noqa: E402
 
 SIGMA = np.array([0.05, 0.05, 0.005, 0.02, 0.0, 0.002])
 SCENARIOS = ("circle4", "frog", "parallel5")
+WEAVE_SECONDS = 2.0      # each half of --obstacle-weave's lane change
+BRAKE_SECONDS = 1000.0   # --obstacle-brake's piece: longer than any obstacle needs to stand
 
 
 def make_scenario(name):
@@ -150,12 +161,26 @@ def main():
         at = argv.index("--obstacle-yaw")
         obstacle_yaw = float(argv[at + 1])
         del argv[at:at + 2]
-    if "--obstacle-seed" in argv:
+    seed_given = "--obstacle-seed" in argv
+    if seed_given:
         at = argv.index("--obstacle-seed")
         obstacle_seed = int(argv[at + 1], 0)
         del argv[at:at + 2]
-        if obstacle_yaw is None:
-            raise SystemExit("--obstacle-seed needs --obstacle-yaw W")
+    man_opt = {"brake": None, "weave": None}
+    for key in man_opt:
+        if f"--obstacle-{key}" in argv:
+            at = argv.index(f"--obstacle-{key}")
+            man_opt[key] = float(argv[at + 1])
+            del argv[at:at + 2]
+    if man_opt["brake"] is not None and man_opt["weave"] is not None:
+        raise SystemExit("--obstacle-brake and --obstacle-weave exclude each other")
+    if man_opt["brake"] is not None and not man_opt["brake"] > 0.0:
+        raise SystemExit("--obstacle-brake DECEL needs DECEL > 0")
+    manoeuvre = man_opt["brake"] is not None or man_opt["weave"] is not None
+    if manoeuvre and obstacle_yaw is None:
+        obstacle_yaw = 0.0           # the scenario's own rows carry the schedule
+    if seed_given and obstacle_yaw is None:
+        raise SystemExit("--obstacle-seed needs --obstacle-yaw W, --obstacle-brake or --obstacle-weave")
     sense = {"pos": None, "heading": 0.0, "drop": 0.0}
     sense_seed = 1
     for key in sense:
@@ -252,10 +277,23 @@ def main():
             osense[..., 0], osense[..., 1] = sense["pos"], sense["heading"]
         sense_kw = dict(sense_kw, obstacle_sensing=osense, sense_seed=sense_seed)
         trk_kw = dict(tracker=TRK.matched(osense))
-    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw, **trk_kw)
+    man_kw = {}
+    if manoeuvre:
+        from scpqp.manoeuvres import ManoeuvreDist
+        half = 0.5 * steps * float(sc.dt)
+        md = ManoeuvreDist(sc.nObst, obstacle_seed).uniform(0, "dur", half, half, lo=0.0)
+        if man_opt["brake"] is not None:
+            md.fixed(1, "dur", BRAKE_SECONDS).fixed(1, "accel", -man_opt["brake"])
+        else:
+            md.fixed(1, "dur", WEAVE_SECONDS).fixed(1, "dyaw", man_opt["weave"])
+            md.fixed(2, "dur", WEAVE_SECONDS).fixed(2, "dyaw", -man_opt["weave"])
+        man_kw = dict(manoeuvres=md.sample(B, device="cuda"))
+    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw, **trk_kw,
+             **man_kw)
     cl.run(1)                      # warm-up (library load, first launches)
     torch.cuda.synchronize()
-    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw, **trk_kw)
+    cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw, **trk_kw,
+             **man_kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     hist = cl.run(steps)
@@ -286,6 +324,9 @@ def main():
         out["variants"] = [{"dsafe_extra": float(values[k]), "metrics": by[k]} for k in sorted(by)]
     if obstacle_yaw is not None:
         out["scenario"], out["obstacle_yaw"], out["obstacle_seed"] = name, obstacle_yaw, obstacle_seed
+    if manoeuvre:
+        out["obstacle_brake"], out["obstacle_weave"] = man_opt["brake"], man_opt["weave"]
+        out["frac_margin_obs_below_dsafe"] = summary["frac_margin_obs_below_0"]
     if track:
         # the same batch and obstacle sensor without the tracker, timed as well
         out["track"] = True
@@ -293,7 +334,7 @@ def main():
         out["trk_p0_yaw"], out["trk_w_clamp"] = TRK.P0_YAW, TRK.W_CLAMP
         nis = torch.cat([h["obst_nis"].flatten() for h in hist])
         out["mean_nis_obst"] = float(nis[~torch.isnan(nis)].mean().item())
-        cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw)
+        cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw, **man_kw)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         plain = cl.run(steps)
@@ -314,11 +355,12 @@ def main():
             out["est_floor"], out["est_q"] = list(EST.FLOOR), q
             nis = torch.cat([h["nis"].flatten() for h in hist])
             out["mean_nis"] = float(nis[~torch.isnan(nis)].mean().item())
-            cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **trk_kw)
+            cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **trk_kw,
+                     **man_kw)
             raw = cl.run(steps)
             out["metrics_raw_sensing"] = cl.metrics_summary()
             out["mean_scp_iters_raw"] = float(np.mean([h["n_scp"].float().mean().item() for h in raw]))
-        cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows)
+        cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **man_kw)
         exact = cl.run(steps)
         out["metrics_exact_sensing"] = cl.metrics_summary()
         out["mean_scp_iters_exact"] = float(np.mean([h["n_scp"].float().mean().item()
@@ -326,7 +368,7 @@ def main():
     if mismatch is not None:
         # the same batch with the nominal plant, untimed: what the mismatch costs
         out["mismatch_pct"], out["truth_seed"] = mismatch, truth_seed
-        cl.reset(x_init, seed=noise_seed, obstacles=rows, **sense_kw, **est_kw, **trk_kw)
+        cl.reset(x_init, seed=noise_seed, obstacles=rows, **sense_kw, **est_kw, **trk_kw, **man_kw)
         cl.run(steps)
         out["metrics_nominal"] = cl.metrics_summary()
         if n_var:

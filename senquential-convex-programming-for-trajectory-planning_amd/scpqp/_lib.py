@@ -1,7 +1,8 @@
 """ctypes binding of ``include/scpqp.h``, ``include/scpqp_noise.h``,
 ``include/scpqp_metrics.h``, ``include/scpqp_variants.h``, ``include/scpqp_truth.h``,
 ``include/scpqp_obstacles.h``, ``include/scpqp_sensing.h``, ``include/scpqp_estimator.h``,
-``include/scpqp_tracker.h`` and ``include/scpqp_manoeuvres.h`` (the C-ABI of the HIP library).
+``include/scpqp_tracker.h``, ``include/scpqp_manoeuvres.h`` and
+``include/scpqp_tracker_accel.h`` (the C-ABI of the HIP library).
 
 The shared library ``libscpqp.so`` is built in-tree (``__graft_entry__.build()``
 or ``python -m scpqp.build``).  There is no CPU fallback: if the library or a
@@ -250,6 +251,19 @@ class ManoeuvreDist(C.Structure):
 MAN_EXPORTS = ("scpqp_manoeuvres_state", "scpqp_manoeuvres_pose", "scpqp_manoeuvres_sample",
                "scpqp_metrics_accumulate_posed")
 
+TRKA_NS = 6
+TRKA_NZ = 4
+TRKA_NP = 14
+(TRKA_R_POS, TRKA_R_HEADING, TRKA_R_SPEED, TRKA_Q_POS, TRKA_Q_HEADING, TRKA_Q_SPEED, TRKA_Q_YAW,
+ TRKA_Q_ACCEL, TRKA_P0_YAW, TRKA_P0_ACCEL, TRKA_W_CLAMP, TRKA_A_CLAMP, TRKA_W_HOLD,
+ TRKA_A_HOLD) = range(TRKA_NP)
+TRKA_FIELDS = ("r_pos", "r_heading", "r_speed", "q_pos", "q_heading", "q_speed", "q_yaw",
+               "q_accel", "p0_yaw", "p0_accel", "w_clamp", "a_clamp", "w_hold", "a_hold")
+TRKA_DPR_SWITCH = 0.3
+
+# every symbol include/scpqp_tracker_accel.h declares (checked by tests/test_tracker_accel_host.py)
+TRKA_EXPORTS = ("scpqp_obstacles_track_accel",)
+
 _lib = None
 
 
@@ -386,6 +400,13 @@ def load(path=None):
         lib.scpqp_manoeuvres_sample.restype = C.c_int
         lib.scpqp_metrics_accumulate_posed.argtypes = [H, I, I, I, I, V, MA, MD, V, V, V, V]
         lib.scpqp_metrics_accumulate_posed.restype = C.c_int
+    # likewise an A/B build from before the tracker with an acceleration state
+    if path is None or hasattr(lib, "scpqp_obstacles_track_accel"):
+        D, I = C.c_double, C.c_int32
+        SS = C.POINTER(SenseStream)
+        lib.scpqp_obstacles_track_accel.argtypes = [I, I, I, V, V, SS, V, D, D, D, D, V, V, V, V, V,
+                                                    V]
+        lib.scpqp_obstacles_track_accel.restype = C.c_int
     if path is None:
         _lib = lib
     return lib

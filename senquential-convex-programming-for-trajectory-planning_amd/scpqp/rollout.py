@@ -38,6 +38,9 @@ and the obstacle prediction (include/scpqp_tracker.h).
 ``reset(..., manoeuvres=)`` makes the obstacles brake, accelerate and turn in pieces on top of
 their rows (include/scpqp_manoeuvres.h); the controller measures them as before and knows
 nothing of the schedule.
+``reset(..., tracker_accel=)`` puts the filter that also estimates the acceleration in the
+tracker's place (include/scpqp_tracker_accel.h): it runs on one manoeuvre piece and predicts a
+horizon that brakes to a stop.
 """
 from __future__ import annotations
 
@@ -197,6 +200,7 @@ class ClosedLoopBatch:
         self.est_rows = None           # the estimator tuning of reset(..., estimator=)
         self.trk_rows = None           # the tracker tuning of reset(..., tracker=)
         self.man_rows = None           # the manoeuvre schedule of reset(..., manoeuvres=)
+        self.trka_rows = None          # the tracker tuning of reset(..., tracker_accel=)
         self.trace = trace     # keep every step's solve inputs and per-SCP-iteration trace
         self.out = self.solver.alloc_out(self.B, trace=trace)
         self.history = []
@@ -208,7 +212,7 @@ class ClosedLoopBatch:
 
     def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0, truth=None,
               obstacles=None, sensing=None, obstacle_sensing=None, sense_seed=None,
-              estimator=None, tracker=None, manoeuvres=None):
+              estimator=None, tracker=None, manoeuvres=None, tracker_accel=None):
         """main.py:73-75: vehiclePathFullRes[:, v, 0] = x0; the control path holds
         scenario.u0 for the first ticks_delay_u + ticks_per_sim + 1 ticks.
 
@@ -267,7 +271,30 @@ class ClosedLoopBatch:
         and predicts from them as before: exact, sensed or tracked.  The metrics and
         ``result_for_plot`` follow the schedule.  Validated here, before anything is launched;
         None, or a schedule in which no piece does anything: nothing is allocated or launched
-        and the rollout is what it was."""
+        and the rollout is what it was.
+
+        ``tracker_accel`` [B, nObst, 14] (scpqp/tracker_accel.py;
+        include/scpqp_tracker_accel.h): the six-state filter per (realisation, obstacle) that
+        also estimates the acceleration, runs on one manoeuvre piece and predicts a horizon
+        that brakes to a stop.  It takes the place of ``tracker=`` (the two together are
+        refused), needs ``obstacles=`` rows, sees the same measurement and the same draws,
+        and records the same keys (``obst_est`` is six wide).  Validated here, before
+        anything is launched; None, or a tuning in which every row is off: nothing is
+        allocated or launched and the rollout is what it was."""
+        if tracker_accel is not None:
+            from . import tracker_accel as TRKA
+            if tracker is not None:
+                raise ValueError("pass either tracker= or tracker_accel=, not both")
+            if obstacles is None:
+                raise ValueError("tracker_accel needs obstacles= rows: pass "
+                                 "obstacles.nominal(scenario, B) for the scenario's own")
+            ta = tracker_accel.detach().cpu().numpy() if isinstance(tracker_accel, torch.Tensor) \
+                else np.asarray(tracker_accel, float)
+            if tuple(ta.shape) != (self.B, self.nO, TRKA.NP):
+                raise ValueError(f"tracker_accel must be [B, nObst, 14] = [{self.B}, {self.nO}, 14]")
+            TRKA.validate(ta)
+            if TRKA.is_off(ta):
+                tracker_accel = None
         if manoeuvres is not None:
             from . import manoeuvres as MAN
             if obstacles is None:
@@ -384,6 +411,11 @@ class ClosedLoopBatch:
         self.trk_x = self.trk_cov = None
         if tracker is not None:
             self.trk_x, self.trk_cov = TRK.alloc(self.B, self.nO, self.device)
+        self.trka_rows = None if tracker_accel is None else torch.as_tensor(
+            tracker_accel, dtype=torch.float64, device=self.device).contiguous().clone()
+        if tracker_accel is not None:
+            # one filter or the other: the state, the tick and the record are shared
+            self.trk_x, self.trk_cov = TRKA.alloc(self.B, self.nO, self.device)
         self.trk_tick = None           # the global tick of the previous obstacle measurement
         self.trk_rec = None            # this step's (estimate, nis, measurement)
         self.man_rows = None if manoeuvres is None else torch.as_tensor(
@@ -414,13 +446,20 @@ class ClosedLoopBatch:
                 from . import manoeuvres as MAN
                 rows, t_meas = MAN.state(self.obst_rows, self.man_rows, t_meas), 0.0
                 self.obst_state = rows
-            if self.trk_rows is not None:
+            if self.trk_rows is not None or self.trka_rows is not None:
                 # the obstacle tracker (include/scpqp_tracker.h): the same measurement,
-                # filtered over the time since the previous one, predicted on its arc
-                from . import tracker as TRK
+                # filtered over the time since the previous one, predicted on its arc; or the
+                # one with an acceleration state (include/scpqp_tracker_accel.h), predicted
+                # on its pieces
+                if self.trka_rows is not None:
+                    from . import tracker_accel as TRK
+                else:
+                    from . import tracker as TRK
                 g0 = tick_meas if self.trk_tick is None else self.trk_tick
                 obst, z, nis = TRK.step(rows, self.osense_rows, self.sense_seed, self.i,
-                                        self.sense_offset, self.trk_rows, t_meas,
+                                        self.sense_offset,
+                                        self.trk_rows if self.trka_rows is None else self.trka_rows,
+                                        t_meas,
                                         (tick_meas - g0) * sc.tick_length,
                                         sc.delay_x + sc.dt + sc.delay_u, sc.dt, self.Hp,
                                         self.trk_x, self.trk_cov)
@@ -551,7 +590,7 @@ class ClosedLoopBatch:
             rec["obst"] = obst      # what the controller was told of the obstacle truth
         if self.man_rows is not None:
             rec["obst_state"] = self.obst_state   # the manoeuvring obstacles at the measurement tick
-        if self.trk_rows is not None:
+        if self.trk_rows is not None or self.trka_rows is not None:
             # the tracker's estimate, its innovations and the obstacle measurement it took
             rec["obst_est"], rec["obst_nis"], rec["obst_meas"] = self.trk_rec
         if self.sense_rows is not None:

@@ -15,7 +15,7 @@ realisation per spawned single-threaded worker.
                                    [--sense-seed S]
                                    [--estimate [--est-q-pos Q] [--est-q-heading Q]
                                     [--est-q-speed Q] [--est-q-steer Q]]]
-                                  [--track]
+                                  [--track | --track-accel [--accel-hold S] [--yaw-hold S]]
                                   [--obstacle-brake DECEL | --obstacle-weave DYAW]
 
 Prints one JSON line: realisation-steps/s on the GPU and the CPU, and the
@@ -64,6 +64,11 @@ the batch is then (``--sense-pos``, ``--sense-heading``, 0) per obstacle, exact 
 reports the timed, tracked run (``metrics``, ``gpu_ms_per_step``, ``mean_nis_obst``) next to the
 same batch and obstacle sensor without the tracker, run and timed after it
 (``metrics_untracked``, ``gpu_ms_per_step_untracked``, ``mean_scp_iters_untracked``).
+``--track-accel`` puts the tracker with an acceleration state
+(include/scpqp_tracker_accel.h) there instead: ``tracker_accel.matched`` rows of the same obstacle
+sensor, with ``--accel-hold S`` and ``--yaw-hold S`` the seconds for which its prediction keeps
+the acceleration and the turn rate (default: longer than any horizon).  It reports what ``--track``
+reports, under the same keys, and excludes ``--track``.
 ``--obstacle-brake DECEL`` gives every (realisation, obstacle) a manoeuvre schedule
 (include/scpqp_manoeuvres.h): it coasts until a start time uniform over the rollout, then brakes
 at DECEL m/s^2 until it stands.  ``--obstacle-weave DYAW`` gives it a lane change at such a start
@@ -212,6 +217,24 @@ def main():
         argv.remove("--track")
         if obstacle_yaw is None:
             raise SystemExit("--track needs --obstacle-yaw W (it tracks the obstacle truth's rows)")
+    track_accel = "--track-accel" in argv
+    holds = {"accel": None, "yaw": None}
+    if track_accel:
+        argv.remove("--track-accel")
+        if track:
+            raise SystemExit("--track and --track-accel exclude each other")
+        if obstacle_yaw is None:
+            raise SystemExit("--track-accel needs --obstacle-yaw W, --obstacle-brake or "
+                             "--obstacle-weave (it tracks the obstacle truth's rows)")
+    for key in holds:
+        if f"--{key}-hold" in argv:
+            at = argv.index(f"--{key}-hold")
+            holds[key] = float(argv[at + 1])
+            del argv[at:at + 2]
+            if not track_accel:
+                raise SystemExit(f"--{key}-hold needs --track-accel")
+            if not holds[key] >= 0.0:
+                raise SystemExit(f"--{key}-hold S needs S >= 0")
     metrics = "--metrics" in argv
     if metrics:
         argv.remove("--metrics")
@@ -270,13 +293,19 @@ def main():
         q = [EST.Q_DEFAULT[k] if est_q[key] is None else est_q[key] for k, key in enumerate(est_q)]
         est_kw = dict(estimator=EST.matched(srows, q=q))
     trk_kw = {}
-    if track:
-        from scpqp import tracker as TRK
+    if track or track_accel:
         osense = torch.zeros((B, sc.nObst, 3), dtype=torch.float64, device="cuda")
         if sense["pos"] is not None:
             osense[..., 0], osense[..., 1] = sense["pos"], sense["heading"]
         sense_kw = dict(sense_kw, obstacle_sensing=osense, sense_seed=sense_seed)
-        trk_kw = dict(tracker=TRK.matched(osense))
+        if track:
+            from scpqp import tracker as TRK
+            trk_kw = dict(tracker=TRK.matched(osense))
+        else:
+            from scpqp import tracker_accel as TRK
+            a_hold = TRK.A_HOLD if holds["accel"] is None else holds["accel"]
+            w_hold = TRK.W_HOLD if holds["yaw"] is None else holds["yaw"]
+            trk_kw = dict(tracker_accel=TRK.matched(osense, a_hold=a_hold, w_hold=w_hold))
     man_kw = {}
     if manoeuvre:
         from scpqp.manoeuvres import ManoeuvreDist
@@ -327,11 +356,14 @@ def main():
     if manoeuvre:
         out["obstacle_brake"], out["obstacle_weave"] = man_opt["brake"], man_opt["weave"]
         out["frac_margin_obs_below_dsafe"] = summary["frac_margin_obs_below_0"]
-    if track:
+    if track or track_accel:
         # the same batch and obstacle sensor without the tracker, timed as well
-        out["track"] = True
+        out["track_accel" if track_accel else "track"] = True
         out["trk_floor"], out["trk_q"] = list(TRK.FLOOR), list(TRK.Q_DEFAULT)
         out["trk_p0_yaw"], out["trk_w_clamp"] = TRK.P0_YAW, TRK.W_CLAMP
+        if track_accel:
+            out["trk_p0_accel"], out["trk_a_clamp"] = TRK.P0_ACCEL, TRK.A_CLAMP
+            out["trk_a_hold"], out["trk_w_hold"] = a_hold, w_hold
         nis = torch.cat([h["obst_nis"].flatten() for h in hist])
         out["mean_nis_obst"] = float(nis[~torch.isnan(nis)].mean().item())
         cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw, **man_kw)

@@ -264,6 +264,12 @@ TRKA_DPR_SWITCH = 0.3
 # every symbol include/scpqp_tracker_accel.h declares (checked by tests/test_tracker_accel_host.py)
 TRKA_EXPORTS = ("scpqp_obstacles_track_accel",)
 
+IMM_MAX_MODES = 4
+IMM_SUM_TOL = 1e-12
+
+# every symbol include/scpqp_imm.h declares (checked by tests/test_imm_host.py)
+IMM_EXPORTS = ("scpqp_obstacles_track_imm",)
+
 _lib = None
 
 
@@ -407,6 +413,13 @@ def load(path=None):
         lib.scpqp_obstacles_track_accel.argtypes = [I, I, I, V, V, SS, V, D, D, D, D, V, V, V, V, V,
                                                     V]
         lib.scpqp_obstacles_track_accel.restype = C.c_int
+    # likewise an A/B build from before the interacting-multiple-model tracker
+    if path is None or hasattr(lib, "scpqp_obstacles_track_imm"):
+        D, I = C.c_double, C.c_int32
+        SS = C.POINTER(SenseStream)
+        lib.scpqp_obstacles_track_imm.argtypes = [I, I, I, I, V, V, SS, V, V, D, D, D, D, V, V, V,
+                                                  V, V, V, V, V]
+        lib.scpqp_obstacles_track_imm.restype = C.c_int
     if path is None:
         _lib = lib
     return lib

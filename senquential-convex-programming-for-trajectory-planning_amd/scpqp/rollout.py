@@ -201,6 +201,7 @@ class ClosedLoopBatch:
         self.trk_rows = None           # the tracker tuning of reset(..., tracker=)
         self.man_rows = None           # the manoeuvre schedule of reset(..., manoeuvres=)
         self.trka_rows = None          # the tracker tuning of reset(..., tracker_accel=)
+        self.imm_rows = None           # the bank (trk, sw) of reset(..., imm=)
         self.trace = trace     # keep every step's solve inputs and per-SCP-iteration trace
         self.out = self.solver.alloc_out(self.B, trace=trace)
         self.history = []
@@ -212,7 +213,7 @@ class ClosedLoopBatch:
 
     def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0, truth=None,
               obstacles=None, sensing=None, obstacle_sensing=None, sense_seed=None,
-              estimator=None, tracker=None, manoeuvres=None, tracker_accel=None):
+              estimator=None, tracker=None, manoeuvres=None, tracker_accel=None, imm=None):
         """main.py:73-75: vehiclePathFullRes[:, v, 0] = x0; the control path holds
         scenario.u0 for the first ticks_delay_u + ticks_per_sim + 1 ticks.
 
@@ -280,7 +281,35 @@ class ClosedLoopBatch:
         refused), needs ``obstacles=`` rows, sees the same measurement and the same draws,
         and records the same keys (``obst_est`` is six wide).  Validated here, before
         anything is launched; None, or a tuning in which every row is off: nothing is
-        allocated or launched and the rollout is what it was."""
+        allocated or launched and the rollout is what it was.
+
+        ``imm`` = (trk [B, nObst, M, 14], sw [B, nObst, M + 1, M]) (scpqp/imm.py;
+        include/scpqp_imm.h): a bank of M six-state filters per (realisation, obstacle) whose
+        probability-weighted prediction becomes the solve's ``obst``.  It takes the place of
+        ``tracker=`` and ``tracker_accel=`` (together with either it is refused), needs
+        ``obstacles=`` rows, and sees the same measurement and the same draws.  The record
+        gains ``obst_est`` (the combined estimate, six wide), ``obst_mu`` and ``obst_nis``
+        ([B, nObst, M]) and ``obst_meas``.  Validated here, before anything is launched; None,
+        or a bank in which every row is off: nothing is allocated or launched and the rollout
+        is what it was."""
+        if imm is not None:
+            from . import imm as IMM
+            if tracker is not None or tracker_accel is not None:
+                raise ValueError("pass one of tracker=, tracker_accel= and imm=, not several")
+            if obstacles is None:
+                raise ValueError("imm needs obstacles= rows: pass "
+                                 "obstacles.nominal(scenario, B) for the scenario's own")
+            try:
+                imm_trk, imm_sw = imm
+            except (TypeError, ValueError):
+                raise ValueError("imm must be a pair (trk, sw)") from None
+            it, isw = (a.detach().cpu().numpy() if isinstance(a, torch.Tensor)
+                       else np.asarray(a, float) for a in (imm_trk, imm_sw))
+            if it.ndim != 4 or tuple(it.shape[:2]) != (self.B, self.nO) or it.shape[3] != IMM.NP:
+                raise ValueError(f"imm trk must be [B, nObst, M, 14] = [{self.B}, {self.nO}, M, 14]")
+            IMM.validate(it, isw)
+            if IMM.is_off(it):
+                imm = None
         if tracker_accel is not None:
             from . import tracker_accel as TRKA
             if tracker is not None:
@@ -416,6 +445,11 @@ class ClosedLoopBatch:
         if tracker_accel is not None:
             # one filter or the other: the state, the tick and the record are shared
             self.trk_x, self.trk_cov = TRKA.alloc(self.B, self.nO, self.device)
+        self.imm_rows = self.imm_state = None
+        if imm is not None:
+            self.imm_rows = tuple(torch.as_tensor(a, dtype=torch.float64, device=self.device)
+                                  .contiguous().clone() for a in (imm_trk, imm_sw))
+            self.imm_state = IMM.alloc(self.B, self.nO, self.imm_rows[0].shape[2], self.device)
         self.trk_tick = None           # the global tick of the previous obstacle measurement
         self.trk_rec = None            # this step's (estimate, nis, measurement)
         self.man_rows = None if manoeuvres is None else torch.as_tensor(
@@ -446,6 +480,20 @@ class ClosedLoopBatch:
                 from . import manoeuvres as MAN
                 rows, t_meas = MAN.state(self.obst_rows, self.man_rows, t_meas), 0.0
                 self.obst_state = rows
+            if self.imm_rows is not None:
+                # the bank of include/scpqp_imm.h: the same measurement and time since the
+                # previous one, every mode filtered, the weighted prediction
+                from . import imm as IMM
+                g0 = tick_meas if self.trk_tick is None else self.trk_tick
+                x_imm, cov, mu = self.imm_state
+                obst, x_hat, z, nis = IMM.step(rows, self.osense_rows, self.sense_seed, self.i,
+                                               self.sense_offset, *self.imm_rows, t_meas,
+                                               (tick_meas - g0) * sc.tick_length,
+                                               sc.delay_x + sc.dt + sc.delay_u, sc.dt, self.Hp,
+                                               x_imm, cov, mu)
+                self.trk_tick = tick_meas
+                self.trk_rec = (x_hat, nis, z, mu.clone())
+                return obst
             if self.trk_rows is not None or self.trka_rows is not None:
                 # the obstacle tracker (include/scpqp_tracker.h): the same measurement,
                 # filtered over the time since the previous one, predicted on its arc; or the
@@ -593,6 +641,9 @@ class ClosedLoopBatch:
         if self.trk_rows is not None or self.trka_rows is not None:
             # the tracker's estimate, its innovations and the obstacle measurement it took
             rec["obst_est"], rec["obst_nis"], rec["obst_meas"] = self.trk_rec
+        if self.imm_rows is not None:
+            # the bank's combined estimate, every mode's innovation and probability
+            rec["obst_est"], rec["obst_nis"], rec["obst_meas"], rec["obst_mu"] = self.trk_rec
         if self.sense_rows is not None:
             rec["x_meas"] = x_meas  # what the controller was told of the vehicles
             rec["delivered"] = delivered

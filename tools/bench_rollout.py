@@ -15,7 +15,8 @@ realisation per spawned single-threaded worker.
                                    [--sense-seed S]
                                    [--estimate [--est-q-pos Q] [--est-q-heading Q]
                                     [--est-q-speed Q] [--est-q-steer Q]]]
-                                  [--track | --track-accel [--accel-hold S] [--yaw-hold S]]
+                                  [--track | --track-accel [--accel-hold S] [--yaw-hold S]
+                                  | --track-imm [--imm-stay P]]
                                   [--obstacle-brake DECEL | --obstacle-weave DYAW]
 
 Prints one JSON line: realisation-steps/s on the GPU and the CPU, and the
@@ -69,6 +70,11 @@ same batch and obstacle sensor without the tracker, run and timed after it
 sensor, with ``--accel-hold S`` and ``--yaw-hold S`` the seconds for which its prediction keeps
 the acceleration and the turn rate (default: longer than any horizon).  It reports what ``--track``
 reports, under the same keys, and excludes ``--track``.
+``--track-imm`` puts the interacting-multiple-model tracker (include/scpqp_imm.h) there instead:
+the default bank of scpqp/imm.py (straight, arc, brake) for the same obstacle sensor, with
+``--imm-stay P`` the chance per call to stay in a mode (default 0.9).  It reports the same keys,
+plus ``imm_modes`` and ``mean_mu`` (the batch mean of every mode's probability over the timed
+run) and ``mean_mu_last`` (at its last step), and excludes ``--track`` and ``--track-accel``.
 ``--obstacle-brake DECEL`` gives every (realisation, obstacle) a manoeuvre schedule
 (include/scpqp_manoeuvres.h): it coasts until a start time uniform over the rollout, then brakes
 at DECEL m/s^2 until it stands.  ``--obstacle-weave DYAW`` gives it a lane change at such a start
@@ -226,6 +232,23 @@ def main():
         if obstacle_yaw is None:
             raise SystemExit("--track-accel needs --obstacle-yaw W, --obstacle-brake or "
                              "--obstacle-weave (it tracks the obstacle truth's rows)")
+    track_imm = "--track-imm" in argv
+    imm_stay = None
+    if track_imm:
+        argv.remove("--track-imm")
+        if track or track_accel:
+            raise SystemExit("--track-imm excludes --track and --track-accel")
+        if obstacle_yaw is None:
+            raise SystemExit("--track-imm needs --obstacle-yaw W, --obstacle-brake or "
+                             "--obstacle-weave (it tracks the obstacle truth's rows)")
+    if "--imm-stay" in argv:
+        at = argv.index("--imm-stay")
+        imm_stay = float(argv[at + 1])
+        del argv[at:at + 2]
+        if not track_imm:
+            raise SystemExit("--imm-stay needs --track-imm")
+        if not 0.0 <= imm_stay <= 1.0:
+            raise SystemExit("--imm-stay P needs 0 <= P <= 1")
     for key in holds:
         if f"--{key}-hold" in argv:
             at = argv.index(f"--{key}-hold")
@@ -293,7 +316,7 @@ def main():
         q = [EST.Q_DEFAULT[k] if est_q[key] is None else est_q[key] for k, key in enumerate(est_q)]
         est_kw = dict(estimator=EST.matched(srows, q=q))
     trk_kw = {}
-    if track or track_accel:
+    if track or track_accel or track_imm:
         osense = torch.zeros((B, sc.nObst, 3), dtype=torch.float64, device="cuda")
         if sense["pos"] is not None:
             osense[..., 0], osense[..., 1] = sense["pos"], sense["heading"]
@@ -301,6 +324,11 @@ def main():
         if track:
             from scpqp import tracker as TRK
             trk_kw = dict(tracker=TRK.matched(osense))
+        elif track_imm:
+            from scpqp import imm as IMM
+            from scpqp import tracker_accel as TRK
+            imm_stay = IMM.STAY if imm_stay is None else imm_stay
+            trk_kw = dict(imm=IMM.bank(osense, stay=imm_stay))
         else:
             from scpqp import tracker_accel as TRK
             a_hold = TRK.A_HOLD if holds["accel"] is None else holds["accel"]
@@ -356,14 +384,21 @@ def main():
     if manoeuvre:
         out["obstacle_brake"], out["obstacle_weave"] = man_opt["brake"], man_opt["weave"]
         out["frac_margin_obs_below_dsafe"] = summary["frac_margin_obs_below_0"]
-    if track or track_accel:
+    if track or track_accel or track_imm:
         # the same batch and obstacle sensor without the tracker, timed as well
-        out["track_accel" if track_accel else "track"] = True
+        out["track_imm" if track_imm else "track_accel" if track_accel else "track"] = True
         out["trk_floor"], out["trk_q"] = list(TRK.FLOOR), list(TRK.Q_DEFAULT)
         out["trk_p0_yaw"], out["trk_w_clamp"] = TRK.P0_YAW, TRK.W_CLAMP
-        if track_accel:
+        if track_accel or track_imm:
             out["trk_p0_accel"], out["trk_a_clamp"] = TRK.P0_ACCEL, TRK.A_CLAMP
+        if track_accel:
             out["trk_a_hold"], out["trk_w_hold"] = a_hold, w_hold
+        if track_imm:
+            out["imm_modes"], out["imm_stay"] = list(IMM.MODES), imm_stay
+            out["imm_quiet"], out["imm_brake_q_accel"] = IMM.QUIET, IMM.BRAKE_Q_ACCEL
+            mu = torch.stack([h["obst_mu"] for h in hist])          # [steps, B, nObst, M]
+            out["mean_mu"] = [float(v) for v in mu.nanmean(dim=(0, 1, 2)).tolist()]
+            out["mean_mu_last"] = [float(v) for v in mu[-1].nanmean(dim=(0, 1)).tolist()]
         nis = torch.cat([h["obst_nis"].flatten() for h in hist])
         out["mean_nis_obst"] = float(nis[~torch.isnan(nis)].mean().item())
         cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw, **man_kw)

@@ -4,6 +4,7 @@
 // so the library builds in parallel) and declared extern below.
 
 #include "scpqp_kernel.h"
+#include "scpqp_margin.h"
 #include "scpqp_variants.h"
 
 #include <vector>
@@ -411,6 +412,7 @@ void fill_block(const scpqp_dims& dims, const scpqp_params* p, DevParams& P) {
         for (int o = 0; o < O; ++o) {
             const double ds = p->dsafe_obs[v * O + o] + p->dsafe_extra;
             P.D2obs[v * SCPQP_MAX_OBST + o] = ds * ds;
+            P.Dobs[v * SCPQP_MAX_OBST + o] = ds;
         }
         const int np = p->ref_npts ? p->ref_npts[v] : 0;
         P.npts[v] = np;
@@ -520,13 +522,16 @@ int scpqp_set_variants(scpqp_handle* h, int32_t n, const scpqp_params* params) {
     return 0;
 }
 
-int scpqp_solve(scpqp_handle* h, int32_t B, const scpqp_batch_in* in, const scpqp_batch_out* out,
-                void* stream) {
+// scpqp_solve, and scpqp_solve_margin of scpqp_margin.h: the same launch with the obstacle
+// margins (ignored without obstacles)
+static int solve_impl(scpqp_handle* h, int32_t B, const scpqp_batch_in* in, const double* margin,
+                      const scpqp_batch_out* out, void* stream) {
     const int rc = check_in(h, B, in, true);
     if (rc) return rc;
     if (!out) return fail(SCPQP_E_ARG, "null output struct%s");
     KArgs a = base_args(B, in);
     a.mode = MODE_SOLVE;
+    a.margin = h->dims.n_obst > 0 ? margin : nullptr;
     a.uOut = out->u;
     a.trajOut = out->traj;
     a.status = out->status;
@@ -541,6 +546,16 @@ int scpqp_solve(scpqp_handle* h, int32_t B, const scpqp_batch_in* in, const scpq
     a.nwarm = out->n_warm;
     a.trace = out->trace;
     return launch(h, a, static_cast<hipStream_t>(stream));
+}
+
+int scpqp_solve(scpqp_handle* h, int32_t B, const scpqp_batch_in* in, const scpqp_batch_out* out,
+                void* stream) {
+    return solve_impl(h, B, in, nullptr, out, stream);
+}
+
+int scpqp_solve_margin(scpqp_handle* h, int32_t B, const scpqp_batch_in* in,
+                       const double* obst_margin, const scpqp_batch_out* out, void* stream) {
+    return solve_impl(h, B, in, obst_margin, out, stream);
 }
 
 int scpqp_linearize(scpqp_handle* h, int32_t B, const scpqp_batch_in* in, const scpqp_lin_out* out,
@@ -560,14 +575,16 @@ int scpqp_linearize(scpqp_handle* h, int32_t B, const scpqp_batch_in* in, const 
     return launch(h, a, static_cast<hipStream_t>(stream));
 }
 
-int scpqp_evaluate(scpqp_handle* h, int32_t B, const scpqp_batch_in* in, const double* u,
-                   const scpqp_eval_out* out, void* stream) {
+static int evaluate_impl(scpqp_handle* h, int32_t B, const scpqp_batch_in* in,
+                         const double* margin, const double* u, const scpqp_eval_out* out,
+                         void* stream) {
     const int rc = check_in(h, B, in, true);
     if (rc) return rc;
     if (B == 0) return 0;
     if (!out || !u) return fail(SCPQP_E_ARG, "null u or output struct%s");
     KArgs a = base_args(B, in);
     a.mode = MODE_EVALUATE;
+    a.margin = h->dims.n_obst > 0 ? margin : nullptr;
     a.uEval = u;
     a.obj = out->obj;
     a.maxv = out->max_violation;
@@ -577,6 +594,17 @@ int scpqp_evaluate(scpqp_handle* h, int32_t B, const scpqp_batch_in* in, const d
     a.cobs = out->c_obs;
     a.trajOut = out->traj;
     return launch(h, a, static_cast<hipStream_t>(stream));
+}
+
+int scpqp_evaluate(scpqp_handle* h, int32_t B, const scpqp_batch_in* in, const double* u,
+                   const scpqp_eval_out* out, void* stream) {
+    return evaluate_impl(h, B, in, nullptr, u, out, stream);
+}
+
+int scpqp_evaluate_margin(scpqp_handle* h, int32_t B, const scpqp_batch_in* in,
+                          const double* obst_margin, const double* u, const scpqp_eval_out* out,
+                          void* stream) {
+    return evaluate_impl(h, B, in, obst_margin, u, out, stream);
 }
 
 int scpqp_sample_reference(scpqp_handle* h, int32_t B, const scpqp_batch_in* in, double* ref,

@@ -120,6 +120,8 @@ struct DevParams {
     double D2obs[SCPQP_MAX_VEH * SCPQP_MAX_OBST];
     double poly[SCPQP_MAX_VEH * SCPQP_MAX_REFPTS * 2];
     int npts[SCPQP_MAX_VEH];
+    double Dobs[SCPQP_MAX_VEH * SCPQP_MAX_OBST];   // dsafe + dsafeExtra, unsquared: the obstacle
+                                                   // margin adds to it (obst_margin of scpqp_margin.h)
 };
 
 enum Mode { MODE_SOLVE = 0, MODE_LINEARIZE = 1, MODE_EVALUATE = 2, MODE_SAMPLE = 3 };
@@ -139,6 +141,8 @@ struct KArgs {
     int* counter;
     const int* perm;   // optional: work item w -> problem perm[w] (longest horizons first)
     const int* variant;   // optional: problem b uses table entry variant[b] (else entry 0)
+    const double* margin; // optional (solve, evaluate; nO > 0): [B][nO][hpMax] metres added to
+                          // the obstacle safety distance (obst_margin of scpqp_margin.h)
 };
 // The kernel argument block, addressed in the constant (kernarg) address space:
 // out-of-line functions take it by pointer without the copy to private memory
@@ -1902,9 +1906,17 @@ struct EvalRes {
     int feasible;
 };
 
+// (D + margin)^2 from the unsquared D = dsafe + dsafeExtra the host keeps next to D2obs
+// (obst_margin of scpqp_margin.h).  The product is rounded on its own, as the host's D * D
+// (never fused into the subtraction that follows it), so a zero margin gives D2obs bitwise.
+__device__ __forceinline__ double d2_with_margin(double D, double margin) {
+    const double Dm = D + margin;
+    return __dmul_rn(Dm, Dm);
+}
+
 template <class LT>
 __device__ EvalRes evaluate_u(const cParams& P, const LT& L, const ldouble* u, double* cveh,
-                              double* cobs) {
+                              double* cobs, const double* mg) {
     const int tid = threadIdx.x, V = L.V, Hb = L.Hb, O = L.O;
     toeplitz_apply(L, u, L.pb);
     bar();
@@ -1934,6 +1946,7 @@ __device__ EvalRes evaluate_u(const cParams& P, const LT& L, const ldouble* u, d
             dx = pi[0] - L.ob[(o * Hb + k) * 2];
             dy = pi[1] - L.ob[(o * Hb + k) * 2 + 1];
             D2 = P.D2obs[i * SCPQP_MAX_OBST + o];
+            if (mg) D2 = d2_with_margin(P.Dobs[i * SCPQP_MAX_OBST + o], mg[o * Hb + k]);
         }
         const double c = D2 - (dx * dx + dy * dy);
         int reps = 1;
@@ -1966,7 +1979,7 @@ __device__ EvalRes evaluate_u(const cParams& P, const LT& L, const ldouble* u, d
 //   nrm = || [a_r uLim, -1] ||,  a_r = -2 d' calB_i,k (+ 2 d' calB_j,k)
 // ---------------------------------------------------------------------------
 template <class LT>
-__device__ void linearise_rows(const cParams& P, const LT& L) {
+__device__ void linearise_rows(const cParams& P, const LT& L, const double* mg) {
     const int tid = threadIdx.x, Hb = L.Hb;
     toeplitz_apply(L, L.ub, L.ya);
     bar();
@@ -1991,6 +2004,7 @@ __device__ void linearise_rows(const cParams& P, const LT& L) {
             dx = pi[0] - L.ob[(o * Hb + k) * 2];
             dy = pi[1] - L.ob[(o * Hb + k) * 2 + 1];
             D2 = P.D2obs[i * SCPQP_MAX_OBST + o];
+            if (mg) D2 = d2_with_margin(P.Dobs[i * SCPQP_MAX_OBST + o], mg[o * Hb + k]);
             au = -2.0 * (dx * yi[0] + dy * yi[1]);
         }
         const double c = D2 - (dx * dx + dy * dy);
@@ -2270,13 +2284,39 @@ PHASE void ph_solve(Ctx c, int dst) {
     LAYDEF;
     chol_solve<SH>(L, L.rhs, dst ? L.dz : L.z);
 }
-PHASE void ph_linearise(Ctx c) {
-    LAYDEF;
-    linearise_rows(P, L);
+// mg: the obstacle margins [O][Hb] of the problem or null, passed by the kernel as an
+// argument (per lane, as Ctx) and workgroup-uniform; shapes compiled without obstacles never
+// look at it
+template <int SH>
+__device__ __forceinline__ const double* uniform_margin(const double* mg) {
+    if constexpr (shape_c(SH).V != 0) return nullptr;
+    else return (const double*)readfirstlane_u64((unsigned long long)mg);
 }
-PHASE EvalRes ph_evaluate(Ctx c, double* cveh, double* cobs) {
+// 1 when the problem's margins hold an entry that is not finite or negative (its own prefix
+// of O * Hb entries only), ORed over the workgroup in the sampler's LDS slot; out of line, so
+// the kernel body's registers are what they were
+PHASE int ph_margin_bad(Ctx c, const double* mg_) {
     LAYDEF;
-    return evaluate_u(P, L, L.ub, cveh, cobs);
+    const double* mg = uniform_margin<SH>(mg_);
+    lint* orslot = (lint*)(L.red + kOrSlot);
+    if (threadIdx.x == 0) *orslot = 0;
+    bar();
+    bool bad = false;
+    if (mg)
+        for (int i = threadIdx.x; i < L.O * L.Hb; i += NT) bad |= !(mg[i] >= 0.0) || mg[i] == INFINITY;
+    if (bad) *orslot = 1;
+    bar();
+    const int any = __builtin_amdgcn_readfirstlane(*orslot);
+    bar();
+    return any;
+}
+PHASE void ph_linearise(Ctx c, const double* mg) {
+    LAYDEF;
+    linearise_rows(P, L, uniform_margin<SH>(mg));
+}
+PHASE EvalRes ph_evaluate(Ctx c, double* cveh, double* cobs, const double* mg) {
+    LAYDEF;
+    return evaluate_u(P, L, L.ub, cveh, cobs, uniform_margin<SH>(mg));
 }
 PHASE D4 ph_residuals(Ctx c) {
     LAYDEF;
@@ -2946,6 +2986,28 @@ __global__ __launch_bounds__(NT, OCC) void scp_kernel(KArgs a) {
         const cParams& P = *Pp;
         const Ctx c{Pp, ws, Hb, lead};
         const int V = P.nV, N = V * Hb, O = P.nO;
+        // the problem's obstacle margins (the host passes them to solve and evaluate only, and
+        // only with obstacles): a non-finite or negative entry in the prefix is reported like
+        // a horizon outside its slot, before anything of the problem is written
+        // (formed from the kernel arguments at every use: not held across the SCP loop)
+        auto margin_ptr = [&]() -> const double* {
+            if constexpr (shape_c(SH).V != 0) return nullptr;
+            else return a.margin ? a.margin + (size_t)b * O * P0.hpMax : nullptr;
+        };
+        if constexpr (shape_c(SH).V == 0) {
+            if (a.margin && PH(ph_margin_bad)(c, margin_ptr())) {
+                if (tid == 0) {
+                    if (a.status) a.status[b] = SCPQP_ST_INVALID;
+                    if (a.nscp) a.nscp[b] = 0;
+                    if (a.nipm) a.nipm[b] = 0;
+                    if (a.npol) a.npol[b] = 0;
+                    if (a.nref) a.nref[b] = 0;
+                    if (a.nwarm) a.nwarm[b] = 0;
+                }
+                bar();
+                continue;
+            }
+        }
 #ifdef SCPQP_PROF
         if (tid == 0 && b < 8192) g_ptime[2 * b] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -2990,7 +3052,7 @@ __global__ __launch_bounds__(NT, OCC) void scp_kernel(KArgs a) {
             if (co)
                 for (int i = tid; i < V * O * Hb; i += NT) co[i] = -INFINITY;
             bar();
-            const EvalRes ev = PH(ph_evaluate)(c, cv, co);
+            const EvalRes ev = PH(ph_evaluate)(c, cv, co, margin_ptr());
             if (tid == 0) {
                 if (a.obj) a.obj[b] = ev.obj;
                 if (a.maxv) a.maxv[b] = ev.maxv;
@@ -3010,7 +3072,7 @@ __global__ __launch_bounds__(NT, OCC) void scp_kernel(KArgs a) {
         bar();
         if (tid == 0 && fabs(lub[0]) < 2.220446049250313e-16) lub[0] = 2.220446049250313e-16;
         bar();
-        EvalRes ev = PH(ph_evaluate)(c, nullptr, nullptr);
+        EvalRes ev = PH(ph_evaluate)(c, nullptr, nullptr, margin_ptr());
         double obj0 = ev.obj, mv0 = ev.maxv;
         const int maxScp = a.maxScp > 0 ? a.maxScp : P.maxScp;
         int qflags = 0, it = 0, status = SCPQP_ST_MAX_SCP;
@@ -3022,7 +3084,7 @@ __global__ __launch_bounds__(NT, OCC) void scp_kernel(KArgs a) {
 #ifdef SCPQP_PROF
             _pt = __builtin_amdgcn_s_memtime();
 #endif
-            PH(ph_linearise)(c);
+            PH(ph_linearise)(c, margin_ptr());
             PROF_ACC(11);
             // warm start from the previous QP's active set from the third QP on: the
             // first re-linearisation moves the active set too far for a few
@@ -3044,7 +3106,7 @@ __global__ __launch_bounds__(NT, OCC) void scp_kernel(KArgs a) {
                                                      : nullptr;
             if (trp) PH(ph_trace_rows)(c, trp);
             PH(ph_take_u)(c);
-            ev = PH(ph_evaluate)(c, nullptr, nullptr);
+            ev = PH(ph_evaluate)(c, nullptr, nullptr, margin_ptr());
             PROF_ACC(17);
             const double merit0 = obj0 + P.slackW * mv0;
             const double delta = merit0 - (ev.obj + P.slackW * ev.maxv);

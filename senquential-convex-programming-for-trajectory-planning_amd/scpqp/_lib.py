@@ -270,6 +270,9 @@ IMM_SUM_TOL = 1e-12
 # every symbol include/scpqp_imm.h declares (checked by tests/test_imm_host.py)
 IMM_EXPORTS = ("scpqp_obstacles_track_imm",)
 
+# every symbol include/scpqp_margin.h declares (checked by tests/test_margin_host.py)
+MARGIN_EXPORTS = ("scpqp_obstacles_margin", "scpqp_solve_margin", "scpqp_evaluate_margin")
+
 _lib = None
 
 
@@ -420,6 +423,17 @@ def load(path=None):
         lib.scpqp_obstacles_track_imm.argtypes = [I, I, I, I, V, V, SS, V, V, D, D, D, D, V, V, V,
                                                   V, V, V, V, V]
         lib.scpqp_obstacles_track_imm.restype = C.c_int
+    # likewise an A/B build from before the obstacle margins
+    if path is None or hasattr(lib, "scpqp_obstacles_margin"):
+        D, I = C.c_double, C.c_int32
+        lib.scpqp_obstacles_margin.argtypes = [I, I, I, I, V, V, V, V, D, D, D, D, V, V, V]
+        lib.scpqp_obstacles_margin.restype = C.c_int
+        lib.scpqp_solve_margin.argtypes = [H, C.c_int32, C.POINTER(BatchIn), V,
+                                           C.POINTER(BatchOut), V]
+        lib.scpqp_solve_margin.restype = C.c_int
+        lib.scpqp_evaluate_margin.argtypes = [H, C.c_int32, C.POINTER(BatchIn), V, V,
+                                              C.POINTER(EvalOut), V]
+        lib.scpqp_evaluate_margin.restype = C.c_int
     if path is None:
         _lib = lib
     return lib

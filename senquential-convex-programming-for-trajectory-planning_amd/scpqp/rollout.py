@@ -59,7 +59,8 @@ CONSTRAINT_TOL = 2 * 2.1 * 1e-3   # Config.py:18
 
 
 def evaluate_in_original_problem(scenario, U, traj, ref_points, obst_future=None,
-                                 tol=CONSTRAINT_TOL, variants=None, variant_of=None):
+                                 tol=CONSTRAINT_TOL, variants=None, variant_of=None,
+                                 obst_margin=None):
     """SCPcontroller.evaluateInOriginalProblem (SCP_controller.py:343-400) for a
     batch, on the device: U [B, Hp, nVeh] (the clipped controller output),
     traj [B, Hp, 2, nVeh] (trajectory prediction), ref_points [B, Hp, 2, nVeh],
@@ -68,7 +69,8 @@ def evaluate_in_original_problem(scenario, U, traj, ref_points, obst_future=None
     predictionFeasible [B] (from the predicted trajectory, as the reference).
     With ``variants`` (a list of scenarios) and ``variant_of`` (an integer device tensor
     [B]), realisation b is weighed with the Q, Q_final, R and dsafe tables of
-    ``variants[variant_of[b]]`` instead of ``scenario``'s."""
+    ``variants[variant_of[b]]`` instead of ``scenario``'s.  ``obst_margin`` [B, nObst, Hp]
+    (scpqp/margin.py): metres added to the obstacle safety distances, as the solve adds them."""
     dev = U.device
     f = dict(dtype=torch.float64, device=dev)
     nV = U.shape[2]
@@ -97,7 +99,11 @@ def evaluate_in_original_problem(scenario, U, traj, ref_points, obst_future=None
     if obst_future is not None and obst_future.shape[1] > 0:
         dso = table(lambda sc: np.asarray(sc.dsafeObstacles, float).reshape(nV, -1) ** 2)
         d2o = ((p[:, :, None] - obst_future[:, None]) ** 2).sum(3)   # [B, nV, nO, Hp]
-        co = dso[:, :, :, None] - d2o
+        if obst_margin is not None:
+            dsm = table(lambda sc: np.asarray(sc.dsafeObstacles, float).reshape(nV, -1))
+            co = (dsm[:, :, :, None] + obst_margin[:, None]) ** 2 - d2o
+        else:
+            co = dso[:, :, :, None] - d2o
         viol = viol | (co > tol).flatten(1).any(1)
         out["constraintValuesObstacle"] = co
     out["predictionFeasible"] = ~viol
@@ -202,6 +208,8 @@ class ClosedLoopBatch:
         self.man_rows = None           # the manoeuvre schedule of reset(..., manoeuvres=)
         self.trka_rows = None          # the tracker tuning of reset(..., tracker_accel=)
         self.imm_rows = None           # the bank (trk, sw) of reset(..., imm=)
+        self.margin = None             # (kappa, m_max) of reset(..., margin=)
+        self.obst_margin = None
         self.trace = trace     # keep every step's solve inputs and per-SCP-iteration trace
         self.out = self.solver.alloc_out(self.B, trace=trace)
         self.history = []
@@ -213,7 +221,8 @@ class ClosedLoopBatch:
 
     def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0, truth=None,
               obstacles=None, sensing=None, obstacle_sensing=None, sense_seed=None,
-              estimator=None, tracker=None, manoeuvres=None, tracker_accel=None, imm=None):
+              estimator=None, tracker=None, manoeuvres=None, tracker_accel=None, imm=None,
+              margin=None):
         """main.py:73-75: vehiclePathFullRes[:, v, 0] = x0; the control path holds
         scenario.u0 for the first ticks_delay_u + ticks_per_sim + 1 ticks.
 
@@ -291,7 +300,26 @@ class ClosedLoopBatch:
         gains ``obst_est`` (the combined estimate, six wide), ``obst_mu`` and ``obst_nis``
         ([B, nObst, M]) and ``obst_meas``.  Validated here, before anything is launched; None,
         or a bank in which every row is off: nothing is allocated or launched and the rollout
-        is what it was."""
+        is what it was.
+
+        ``margin`` = (kappa, m_max) (scpqp/margin.py; include/scpqp_margin.h): after every
+        tracker step the tracker's covariances become a safety margin per (realisation,
+        obstacle, horizon step), ``min(kappa sigma, m_max)`` metres, which the solve (and the
+        evaluation of ``evaluate=True``) adds to its obstacle safety distances.  It needs
+        ``tracker_accel=`` or ``imm=`` (the five-state ``tracker=`` has no acceleration row).
+        The record gains ``obst_margin`` [B, nObst, Hp].  The realised-path metrics stay what
+        they are: they measure the truth, not the inflated distance.  None: the rollout is
+        what it was; ``(0, m_max)`` gives the same rollout bitwise."""
+        if margin is not None:
+            from . import margin as MG
+            if tracker_accel is None and imm is None:
+                raise ValueError("margin needs tracker_accel= or imm=: the margin is taken from "
+                                 "a six-state tracker's covariance")
+            try:
+                kappa, m_max = margin
+            except (TypeError, ValueError):
+                raise ValueError("margin must be a pair (kappa, m_max)") from None
+            margin = MG.validate(kappa, m_max)
         if imm is not None:
             from . import imm as IMM
             if tracker is not None or tracker_accel is not None:
@@ -450,6 +478,9 @@ class ClosedLoopBatch:
             self.imm_rows = tuple(torch.as_tensor(a, dtype=torch.float64, device=self.device)
                                   .contiguous().clone() for a in (imm_trk, imm_sw))
             self.imm_state = IMM.alloc(self.B, self.nO, self.imm_rows[0].shape[2], self.device)
+        # (kappa, m_max) of reset(..., margin=); without a filter there is nothing to take it from
+        self.margin = margin if (tracker_accel is not None or imm is not None) else None
+        self.obst_margin = None        # this step's margins [B, nObst, Hp]
         self.trk_tick = None           # the global tick of the previous obstacle measurement
         self.trk_rec = None            # this step's (estimate, nis, measurement)
         self.man_rows = None if manoeuvres is None else torch.as_tensor(
@@ -493,6 +524,11 @@ class ClosedLoopBatch:
                                                x_imm, cov, mu)
                 self.trk_tick = tick_meas
                 self.trk_rec = (x_hat, nis, z, mu.clone())
+                if self.margin is not None:
+                    from . import margin as MG
+                    self.obst_margin = MG.step(self.imm_rows[0], x_imm, cov, mu,
+                                               sc.delay_x + sc.dt + sc.delay_u, sc.dt, self.Hp,
+                                               *self.margin)
                 return obst
             if self.trk_rows is not None or self.trka_rows is not None:
                 # the obstacle tracker (include/scpqp_tracker.h): the same measurement,
@@ -513,6 +549,11 @@ class ClosedLoopBatch:
                                         self.trk_x, self.trk_cov)
                 self.trk_tick = tick_meas
                 self.trk_rec = (self.trk_x.clone(), nis, z)
+                if self.margin is not None:
+                    from . import margin as MG
+                    self.obst_margin = MG.step(self.trka_rows, self.trk_x, self.trk_cov, None,
+                                               sc.delay_x + sc.dt + sc.delay_u, sc.dt, self.Hp,
+                                               *self.margin)
                 return obst
             if self.osense_rows is not None:
                 # the sensing truth: the same extrapolation from a noisy pose and speed
@@ -603,7 +644,7 @@ class ClosedLoopBatch:
         # the draws of comp_jacobian's one ode call (Model.py:58)
         ec_noise = None if rng is None else PL.draw_ec_noise(rng, B, nV, self.device)
         out = self.solver.solve(x0, u_hold, ec_noise, u_warm=u_warm, obst=obst, out=self.out,
-                                variant=self.variant_of)
+                                variant=self.variant_of, obst_margin=self.obst_margin)
         self.u_prev = out.u.clone()
         if self.timing:
             torch.cuda.synchronize(self.device)
@@ -644,6 +685,8 @@ class ClosedLoopBatch:
         if self.imm_rows is not None:
             # the bank's combined estimate, every mode's innovation and probability
             rec["obst_est"], rec["obst_nis"], rec["obst_meas"], rec["obst_mu"] = self.trk_rec
+        if self.obst_margin is not None:
+            rec["obst_margin"] = self.obst_margin   # what the solve added to its safety distances
         if self.sense_rows is not None:
             rec["x_meas"] = x_meas  # what the controller was told of the vehicles
             rec["delivered"] = delivered
@@ -658,7 +701,8 @@ class ClosedLoopBatch:
             rec["ref"] = ref
             rec["evaluation"] = evaluate_in_original_problem(
                 sc, U.view(B, nV, Hp).transpose(1, 2), rec["traj"], ref, obst,
-                variants=self.variants, variant_of=self.variant_of)
+                variants=self.variants, variant_of=self.variant_of,
+                obst_margin=self.obst_margin)
         if self.keep_path:
             rec["path"] = path
             rec["delay_traj"] = dtraj

@@ -181,7 +181,7 @@ class ScpQpSolver:
         return torch.as_tensor(np.ascontiguousarray(x), dtype=dtype, device=self.device)
 
     def _inputs(self, x0, u0=None, ec_noise=None, hp=None, obst=None, ref_points=None,
-                u_warm=None, max_scp_iter=0, need_obst=True, variant=None):
+                u_warm=None, max_scp_iter=0, need_obst=True, variant=None, obst_margin=None):
         """Move the inputs to the device and check every size against (B, nVeh, nObst,
         hp_max) before anything is launched: the kernel indexes each per-problem slot
         with hp_max strides.  Per-problem slots are sized for hp_max; a problem of
@@ -217,7 +217,9 @@ class ScpQpSolver:
         _need(uw, B * nV * Hm, "u_warm [B, nVeh*hp_max] (packed per slot)")
         var = self._dev(variant, torch.int32)
         _need(var, B, "variant [B]")
-        bufs = (x0, u0, ec, hpt, ob, rp, uw, var)
+        mg = self._dev(obst_margin) if nO else None
+        _need(mg, B * nO * Hm, "obst_margin [B, nObst, hp_max] (packed per slot)")
+        bufs = (x0, u0, ec, hpt, ob, rp, uw, var, mg)
         bi = LB.BatchIn(x0=_vptr(x0), u0=_vptr(u0), ec_noise=_vptr(ec), hp=_vptr(hpt),
                         obst=_vptr(ob), ref_points=_vptr(rp), u_warm=_vptr(uw),
                         max_scp_iter=int(max_scp_iter), reserved=0, variant=_vptr(var))
@@ -228,7 +230,7 @@ class ScpQpSolver:
 
     # ------------------------------------------------------------------ entry points
     def solve(self, x0, u0=None, ec_noise=None, hp=None, obst=None, ref_points=None, u_warm=None,
-              max_scp_iter=0, out=None, trace=False, variant=None):
+              max_scp_iter=0, out=None, trace=False, variant=None, obst_margin=None):
         """SCP_controller for a batch.  Arrays: x0 [B,nVeh,6], u0 [B,nVeh], ec_noise [B,nVeh,2],
         hp [B] int, obst [B,nObst,2,hp_max], ref_points [B,hp_max,2,nVeh], u_warm
         [B,nVeh*hp_max]; per-problem slots are read as packed prefixes for hp_b < hp_max
@@ -236,9 +238,14 @@ class ScpQpSolver:
         optimization_log, SCP_controller.py:169-189) into ``out.trace``; decode it with
         scpqp.trace.decode.  ``variant`` [B] int: problem b uses entry ``variant[b]`` of the
         table of ``set_variants`` (None: entry 0); an index outside the table gives
-        ST_INVALID with zero counters, like a horizon outside its slot."""
+        ST_INVALID with zero counters, like a horizon outside its slot.  ``obst_margin``
+        [B,nObst,hp_max] (packed per slot, as obst): metres added to the obstacle safety
+        distance of problem b, obstacle o, horizon step k (scpqp.margin.step writes such an
+        array; None: 0, the plain scpqp_solve; else scpqp_solve_margin of scpqp_margin.h); a
+        problem with a non-finite or negative entry gives ST_INVALID likewise.  Ignored
+        without obstacles."""
         B, bi, bufs = self._inputs(x0, u0, ec_noise, hp, obst, ref_points, u_warm, max_scp_iter,
-                                   variant=variant)
+                                   variant=variant, obst_margin=obst_margin)
         if out is None:
             out = self.alloc_out(B, trace=trace)
         self._check_out(out, B)
@@ -248,8 +255,13 @@ class ScpQpSolver:
                          sum_violations=_vptr(out.sum_violations), feasible=_vptr(out.feasible),
                          n_polish=_vptr(out.n_polish), n_refine=_vptr(out.n_refine),
                          n_warm=_vptr(out.n_warm), trace=_vptr(out.trace))
-        LB.check(self.lib.scpqp_solve(self.h, B, C.byref(bi), C.byref(bo), self._stream()),
-                 self.lib)
+        mg = bufs[-1]
+        if mg is None:
+            rc = self.lib.scpqp_solve(self.h, B, C.byref(bi), C.byref(bo), self._stream())
+        else:
+            rc = self.lib.scpqp_solve_margin(self.h, B, C.byref(bi), _vptr(mg), C.byref(bo),
+                                             self._stream())
+        LB.check(rc, self.lib)
         self._last_inputs = bufs   # keep device inputs alive until the stream consumes them
         return out
 
@@ -311,8 +323,9 @@ class ScpQpSolver:
         return res
 
     def evaluate(self, u, x0, u0=None, ec_noise=None, hp=None, obst=None, ref_points=None,
-                 variant=None):
-        B, bi, bufs = self._inputs(x0, u0, ec_noise, hp, obst, ref_points, variant=variant)
+                 variant=None, obst_margin=None):
+        B, bi, bufs = self._inputs(x0, u0, ec_noise, hp, obst, ref_points, variant=variant,
+                                   obst_margin=obst_margin)
         nV, nO, Hm, dev = self.nV, self.nO, self.hp_max, self.device
         ut = self._dev(u).reshape(B, -1)
         if ut.shape[1] < nV * Hm:
@@ -325,8 +338,15 @@ class ScpQpSolver:
                    c_veh=torch.zeros(B, nV, nV, Hm, **f), c_obs=torch.zeros(B, nV, max(nO, 1), Hm, **f),
                    traj=torch.zeros(B, Hm, 2, nV, **f))
         eo = LB.EvalOut(**{k: _vptr(v) for k, v in res.items()})
-        LB.check(self.lib.scpqp_evaluate(self.h, B, C.byref(bi), C.c_void_p(ut.data_ptr()),
-                                         C.byref(eo), self._stream()), self.lib)
+        mg = bufs[-1]
+        if mg is None:
+            rc = self.lib.scpqp_evaluate(self.h, B, C.byref(bi), C.c_void_p(ut.data_ptr()),
+                                         C.byref(eo), self._stream())
+        else:
+            rc = self.lib.scpqp_evaluate_margin(self.h, B, C.byref(bi), _vptr(mg),
+                                                C.c_void_p(ut.data_ptr()), C.byref(eo),
+                                                self._stream())
+        LB.check(rc, self.lib)
         torch.cuda.current_stream(dev).synchronize()
         return res
 

@@ -18,6 +18,7 @@ realisation per spawned single-threaded worker.
                                   [--track | --track-accel [--accel-hold S] [--yaw-hold S]
                                   | --track-imm [--imm-stay P]]
                                   [--obstacle-brake DECEL | --obstacle-weave DYAW]
+                                  [--margin-kappa K [--margin-max M]]
 
 Prints one JSON line: realisation-steps/s on the GPU and the CPU, and the
 largest state difference between the two on the CPU sample.  ``--noise-seed S``
@@ -83,6 +84,11 @@ time instead: DYAW rad/s more for WEAVE_SECONDS, then DYAW less for as long.  Bo
 included.  Without ``--obstacle-yaw`` the rows are the scenario's own (``--obstacle-yaw 0``);
 ``--track`` is accepted with either.  They imply ``--metrics``; the CPU sample keeps the straight
 obstacles.
+``--margin-kappa K`` turns the tracker's covariances into obstacle safety margins
+(include/scpqp_margin.h; ``reset(..., margin=(K, M))``) of at most ``--margin-max M`` metres
+(default MARGIN_MAX); it needs ``--track-accel`` or ``--track-imm`` and adds ``mean_margin``,
+``mean_margin_last_horizon_step`` and ``frac_margin_at_max``.  ``frac_steps_at_scp_cap`` (every
+run) is the share of solves that ran into the SCP iteration cap.
 """
 import json
 import multiprocessing as mp
@@ -99,6 +105,7 @@ SIGMA = np.array([0.05, 0.05, 0.005, 0.02, 0.0, 0.002])
 SCENARIOS = ("circle4", "frog", "parallel5")
 WEAVE_SECONDS = 2.0      # each half of --obstacle-weave's lane change
 BRAKE_SECONDS = 1000.0   # --obstacle-brake's piece: longer than any obstacle needs to stand
+MARGIN_MAX = 2.0         # metres: --margin-max's default, a choice (half an obstacle's length)
 
 
 def make_scenario(name):
@@ -249,6 +256,24 @@ def main():
             raise SystemExit("--imm-stay needs --track-imm")
         if not 0.0 <= imm_stay <= 1.0:
             raise SystemExit("--imm-stay P needs 0 <= P <= 1")
+    margin = None
+    if "--margin-kappa" in argv:
+        at = argv.index("--margin-kappa")
+        kappa = float(argv[at + 1])
+        del argv[at:at + 2]
+        m_max = MARGIN_MAX
+        if "--margin-max" in argv:
+            at = argv.index("--margin-max")
+            m_max = float(argv[at + 1])
+            del argv[at:at + 2]
+        if not (track_accel or track_imm):
+            raise SystemExit("--margin-kappa needs --track-accel or --track-imm (the margin is "
+                             "taken from a six-state tracker's covariance)")
+        if not (kappa >= 0.0 and m_max >= 0.0 and np.isfinite(kappa) and np.isfinite(m_max)):
+            raise SystemExit("--margin-kappa K and --margin-max M need finite K, M >= 0")
+        margin = (kappa, m_max)
+    elif "--margin-max" in argv:
+        raise SystemExit("--margin-max needs --margin-kappa")
     for key in holds:
         if f"--{key}-hold" in argv:
             at = argv.index(f"--{key}-hold")
@@ -334,6 +359,8 @@ def main():
             a_hold = TRK.A_HOLD if holds["accel"] is None else holds["accel"]
             w_hold = TRK.W_HOLD if holds["yaw"] is None else holds["yaw"]
             trk_kw = dict(tracker_accel=TRK.matched(osense, a_hold=a_hold, w_hold=w_hold))
+    if margin is not None:
+        trk_kw["margin"] = margin
     man_kw = {}
     if manoeuvre:
         from scpqp.manoeuvres import ManoeuvreDist
@@ -372,6 +399,9 @@ def main():
         "max_state_diff_vs_cpu": diff,
         "predicted_feasible_frac": feas,
         "mean_scp_iters": float(np.mean([h["n_scp"].float().mean().item() for h in hist])),
+        # the share of (realisation, step) solves that ran into the SCP iteration cap
+        "frac_steps_at_scp_cap": float(np.mean([(h["n_scp"] >= R.MAX_SCP_ITER).float().mean().item()
+                                                for h in hist])),
     }
     if metrics:
         out["metrics"] = summary
@@ -399,6 +429,12 @@ def main():
             mu = torch.stack([h["obst_mu"] for h in hist])          # [steps, B, nObst, M]
             out["mean_mu"] = [float(v) for v in mu.nanmean(dim=(0, 1, 2)).tolist()]
             out["mean_mu_last"] = [float(v) for v in mu[-1].nanmean(dim=(0, 1)).tolist()]
+        if margin is not None:
+            mg = torch.stack([h["obst_margin"] for h in hist])      # [steps, B, nObst, Hp]
+            out["margin_kappa"], out["margin_max"] = margin
+            out["mean_margin"] = float(mg.nanmean().item())
+            out["mean_margin_last_horizon_step"] = float(mg[..., -1].nanmean().item())
+            out["frac_margin_at_max"] = float((mg == margin[1]).float().mean().item())
         nis = torch.cat([h["obst_nis"].flatten() for h in hist])
         out["mean_nis_obst"] = float(nis[~torch.isnan(nis)].mean().item())
         cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw, **man_kw)

@@ -1,7 +1,9 @@
 """Bitwise A/B of two builds of the library on one configuration: solve the same batch
 with each (one process per library, _lib.use_build) and compare every output array exactly.
 
-    python tools/bitwise_ab.py <config c2|c4|c5|c3> <lib_a.so> <lib_b.so> [batch]
+    python tools/bitwise_ab.py <config c2|c4|c5|c3|frog> <lib_a.so> <lib_b.so> [batch]
+
+``frog`` is the frog scenario (1 vehicle, 22 obstacles, Hp 10): the obstacle rows of the solve.
 """
 import os
 import subprocess
@@ -14,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "senquential-convex-programming-for-trajectory-planning_amd")]
 
 CFG = {"c2": (4, 20, 1024, None), "c4": (4, 20, 8192, None), "c3": (8, 30, 4096, None),
-       "c5": (4, 30, 3072, (10, 20, 30))}
+       "c5": (4, 30, 3072, (10, 20, 30)), "frog": (1, 10, 1024, None)}
 
 
 def run_one(cfg, out_path, batch, lib):
@@ -28,11 +30,15 @@ def run_one(cfg, out_path, batch, lib):
     B = batch or B
     sc = Scenarios.Scenario(False)
     sc.Hp = sc.Hu = hp
-    sc.get_circle_scenario([2 * np.pi / nv * (i + 1) for i in range(nv)])
+    if cfg == "frog":
+        sc.get_frog_scenario()
+    else:
+        sc.get_circle_scenario([2 * np.pi / nv * (i + 1) for i in range(nv)])
     sc.complete_scenario()
     bt = shard.shard_batch(sc, B, 0, base_seed=0, mixed_hp=mixed)
     S = ScpQpSolver(sc, max_batch=B)
-    out = S.solve(bt.x0, bt.u0, bt.ec_noise, hp=bt.hp if mixed else None)
+    out = S.solve(bt.x0, bt.u0, bt.ec_noise, hp=bt.hp if mixed else None,
+                  obst=bt.obst if sc.nObst else None)
     torch.cuda.synchronize()
     np.savez(out_path, **{k: getattr(out, k).cpu().numpy() for k in
                           ("u", "traj", "status", "n_scp", "n_ipm", "obj", "max_violation",

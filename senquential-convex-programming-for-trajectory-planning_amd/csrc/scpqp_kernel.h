@@ -46,6 +46,7 @@
 
 #include <new>
 #include <type_traits>
+#include <utility>
 
 #include "scpqp.h"
 
@@ -1396,12 +1397,23 @@ __device__ __forceinline__ void panel_factor(HP H, ldouble* dinv, int n, int r0,
             }
         }
     }
+    // Only where a padded value can reach something that is stored, broadcast or written to
+    // ldbuf, which is the last panel (jb < CB) alone.  With jb == CB every column is one of
+    // the panel and rows r0 .. r0 + 7 are below n, so the padding could only change rows
+    // >= n, which hold copies of the clamped row n - 1 (finite).  No such row is broadcast
+    // (the readlanes below take lanes 0 .. 7 of slot 0) or stored (the stores are under
+    // i < n), and dinv, dout and the failure flag come from the broadcast block.  Such a row
+    // can be one of the look-ahead rows r0 + 8 + c written to ldbuf (n - r0 < 16); then c >=
+    // n - r0 - 8 = the next panel's jb < CB, and ldbuf row c only enters that panel's column
+    // c, which that panel pads before it uses it.  Wave-uniform, so a scalar branch.
+    if (jb < CB) {
 #pragma unroll
-    for (int t = 0; t < RS; ++t) {
-        const int i = r0 + lane + 64 * t;
+        for (int t = 0; t < RS; ++t) {
+            const int i = r0 + lane + 64 * t;
 #pragma unroll
-        for (int c = 0; c < CB; ++c)
-            p[t][c] = (i < n && c < jb) ? p[t][c] : ((t == 0 && lane == c) ? 1.0 : 0.0);
+            for (int c = 0; c < CB; ++c)
+                p[t][c] = (i < n && c < jb) ? p[t][c] : ((t == 0 && lane == c) ? 1.0 : 0.0);
+        }
     }
     PROF_ACC_FINE(19);
     if (jb == 1) {
@@ -1719,17 +1731,68 @@ __device__ bool cholesky(const LT& L) {
 // streamed 4 columns (forward) / 4 rows (backward) at a time into registers,
 // double-buffered, so the LDS latency hides behind the dependent steps.
 // (Measured alternatives, tools/probe/solve_probe.hip and DESIGN §3: ping-pong
-// buffers with bounds-free full chunks, v_writelane capture, and a blocked
-// variant that solves 8 x 8 diagonal blocks on uniform values; the first two
-// are faster in isolation but slower inside the kernel, the third is slower.)
+// buffers with bounds-free full chunks, and a blocked variant that solves 8 x 8
+// diagonal blocks on uniform values; the first is faster in isolation but slower
+// inside the kernel, the second is slower.)
 // ---------------------------------------------------------------------------
 
 constexpr int kSolveChunk = 4;    // chunk of a factor in LDS
 constexpr int kSolveChunkG = 8;   // chunk of a factor in the workspace: twice the steps cover the L2 latency
-template <int R, class HP, int SCH, bool RTN = false>
-struct Solver {   // SCH: chunk (columns / rows) streamed per step group; RTN: n not a
-                  // compile-time constant (the chunk loops stay rolled, below)
+// One substitution step's lane traffic as a single asm statement, lanes immediate (no M0, no
+// lane mask, no select): the broadcast of lane LN of v (returned, uniform; its halves also
+// left in blo / bhi), and, when LP >= 0, the capture of the previous step's broadcast
+// (blo / bhi on entry) into lane LP of dst.  The compiler neither counts an asm's
+// instructions as wait states nor pads hazards against them, so the statement carries its
+// own (gfx950: a VALU write of a VGPR, one state, v_readlane of it; a VALU write of an
+// SGPR, two states, a VALU reading it):
+//   s_nop 0        the caller's FMA into v may be the instruction before
+//   v_readlane x2
+//   v_writelane x2 of the PREVIOUS broadcast, whose SGPRs are long written.  They are the two
+//                  states between the readlanes and the caller's FMA that reads the new
+//                  broadcast; capturing the new one here would need two more states in front
+//                  of it and two behind.  Without a previous step, s_nop 1 stands in.
+// flush_lane_d captures the last broadcast of a sweep: every step statement ends two states
+// after its second readlane, so it needs no padding either.
+template <int LN, int LP>
+__device__ __forceinline__ double bcast_capture_d(double v, double& dst, int& blo, int& bhi) {
+    static_assert(LN >= 0 && LN < 64 && LP < 64, "lanes of the wave");
+    const long long b = __double_as_longlong(v);
+    const int vlo = static_cast<int>(b & 0xffffffffll), vhi = static_cast<int>(b >> 32);
+    int lo, hi;
+    if constexpr (LP >= 0) {
+        const long long d = __double_as_longlong(dst);
+        int dlo = static_cast<int>(d & 0xffffffffll), dhi = static_cast<int>(d >> 32);
+        asm("s_nop 0\n\tv_readlane_b32 %0, %4, %8\n\tv_readlane_b32 %1, %5, %8\n\t"
+            "v_writelane_b32 %2, %6, %9\n\tv_writelane_b32 %3, %7, %9"
+            : "=&s"(lo), "=&s"(hi), "+v"(dlo), "+v"(dhi)
+            : "v"(vlo), "v"(vhi), "s"(blo), "s"(bhi), "i"(LN), "i"(LP));
+        dst = __longlong_as_double((static_cast<long long>(dhi) << 32) | static_cast<unsigned int>(dlo));
+    } else {
+        asm("s_nop 0\n\tv_readlane_b32 %0, %2, %4\n\tv_readlane_b32 %1, %3, %4\n\ts_nop 1"
+            : "=&s"(lo), "=&s"(hi)
+            : "v"(vlo), "v"(vhi), "i"(LN));
+    }
+    blo = lo;
+    bhi = hi;
+    return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo));
+}
+template <int LP>
+__device__ __forceinline__ void flush_lane_d(double& dst, int blo, int bhi) {
+    static_assert(LP >= 0 && LP < 64, "a lane of the wave");
+    const long long d = __double_as_longlong(dst);
+    int dlo = static_cast<int>(d & 0xffffffffll), dhi = static_cast<int>(d >> 32);
+    asm("v_writelane_b32 %0, %2, %4\n\tv_writelane_b32 %1, %3, %4"
+        : "+v"(dlo), "+v"(dhi)
+        : "s"(blo), "s"(bhi), "i"(LP));
+    dst = __longlong_as_double((static_cast<long long>(dhi) << 32) | static_cast<unsigned int>(dlo));
+}
+template <int R, class HP, int SCH, int NC = 0>
+struct Solver {   // SCH: chunk (columns / rows) streamed per step group; NC: n as a
+                  // compile-time constant, or 0 when it is known at run time only (the
+                  // chunk loops stay rolled, below)
+    static constexpr bool RTN = NC == 0;
     static_assert(SCH % 2 == 0 && 64 % SCH == 0, "chunks tile the 64-row slots");
+    static_assert(NC <= 64 * R, "every row has a slot");
     HP H;                   // factor (LDS or workspace)
     const ldouble* dinv;
     int lane, n, ld;
@@ -1778,18 +1841,79 @@ struct Solver {   // SCH: chunk (columns / rows) streamed per step group; RTN: n
 #pragma unroll
             for (int q = 0; q < SCH; ++q) cur[t][q] = nxt[t][q];
     }
-    // the solution entry j (uniform xj) into its owner lane (v_writelane through M0 is
-    // bitwise the same but kept the sweep from unrolling: solves 21.2k -> 31.3k cycles per
-    // IPM iteration at B = 1, c2 -7 %, profiles/r05_ab_writelane.txt)
+    // The solution entry j (uniform xj) into its owner lane.  With n known at run time only
+    // this is a select on lane == (j & 63): a v_cmp whose 64-bit mask the compiler hoists
+    // and spills into VGPR lanes, two v_mov (the select's one scalar source is the mask) and
+    // two v_cndmask per step, more instructions than the substitution itself.  (v_writelane
+    // with the lane in M0 is bitwise the same but lost, solves 21.2k -> 31.3k cycles per IPM
+    // iteration at B = 1, c2 -7 %, profiles/r05_ab_writelane.txt: the asm with its M0 write
+    // kept the compiler from unrolling the sweep, so the rolled loop paid the M0 write, the
+    // chunk branch and run-time row indices at every step.  That measured the lost
+    // unrolling, not the writelane.)  With n a compile-time constant the step index is a
+    // template argument, below, and the capture is a v_writelane with an immediate lane.
     __device__ __forceinline__ double capture(double xj, int j, double old) const {
         return (lane == (j & 63)) ? xj : old;
+    }
+    // --- n a compile-time constant: every chunk and step index is a template argument (an
+    // index-sequence fold, nothing is left to the unroller).  The same operations in the same
+    // order as the loops below, except that a step's capture rides in the next step's
+    // broadcast statement (bcast_capture_d) and the last one of a slot's sweep is flushed.
+    int blo, bhi;   // the last broadcast's halves (uniform)
+    template <int T, int J, int Q>
+    __device__ __forceinline__ void fwd_step() {
+        if constexpr (J < (NC < 64 * (T + 1) ? NC : 64 * (T + 1))) {
+            const double xj = bcast_capture_d<(J & 63), (J == 64 * T ? -1 : ((J - 1) & 63))>(r[T], xf[T], blo, bhi);
+            r[T] -= cur[T][Q] * xj;
+#pragma unroll
+            for (int t = T + 1; t < R; ++t) r[t] -= cur[t][Q] * xj;
+        }
+    }
+    template <int T, int JC, int... Q>
+    __device__ __forceinline__ void fwd_chunk(std::integer_sequence<int, Q...>) {
+        if constexpr (JC + SCH < NC) load_cols(nxt, JC + SCH);
+        (fwd_step<T, JC + Q, Q>(), ...);
+        shift();
+    }
+    template <int T, int... C>
+    __device__ __forceinline__ void fwd_chunks(std::integer_sequence<int, C...>) {
+        (fwd_chunk<T, 64 * T + SCH * C>(std::make_integer_sequence<int, SCH>{}), ...);
+    }
+    template <int T, int J, int Q>
+    __device__ __forceinline__ void bwd_step() {
+        if constexpr (J < NC) {
+            constexpr int jfirst = NC - 1 < 64 * T + 63 ? NC - 1 : 64 * T + 63;
+            const double xj = bcast_capture_d<(J & 63), (J == jfirst ? -1 : ((J + 1) & 63))>(r[T], xf[T], blo, bhi);
+            // the owner slot first: it carries the next step's broadcast
+            r[T] -= cur[T][Q] * xj;
+#pragma unroll
+            for (int t = 0; t < T; ++t) r[t] -= cur[t][Q] * xj;
+        }
+    }
+    template <int T, int JC, int... Q>
+    __device__ __forceinline__ void bwd_chunk(std::integer_sequence<int, Q...>) {
+        if constexpr (JC > 0) load_rows(nxt, JC - SCH);
+        (bwd_step<T, JC + SCH - 1 - Q, SCH - 1 - Q>(), ...);
+        shift();
+    }
+    template <int T, int JSTART, int... C>
+    __device__ __forceinline__ void bwd_chunks(std::integer_sequence<int, C...>) {
+        (bwd_chunk<T, JSTART - SCH * C>(std::make_integer_sequence<int, SCH>{}), ...);
     }
     // forward over the columns owned by slot T (compile-time owner); slots < T are final
     template <int T>
     __device__ __forceinline__ void fwd() {
-        if constexpr (T < R) {
+        if constexpr (T < R && !RTN) {
+            constexpr int jend = NC < 64 * (T + 1) ? NC : 64 * (T + 1);
+            constexpr int nch = jend > 64 * T ? (jend - 64 * T + SCH - 1) / SCH : 0;
+            fwd_chunks<T>(std::make_integer_sequence<int, nch>{});
+            if constexpr (nch > 0) flush_lane_d<((jend - 1) & 63)>(xf[T], blo, bhi);
+        } else if constexpr (T < R) {
             const int jend = min(n, 64 * (T + 1));
-            auto chunk = [&](int jc) {
+            // with a run-time n the compiler unrolled this loop once per possible
+            // remainder (248 VGPRs, stack reloads inside the sweep: c5's mixed
+            // horizons); rolled it stays one chunk body
+#pragma unroll 1
+            for (int jc = 64 * T; jc < jend; jc += SCH) {
                 if (jc + SCH < n) load_cols(nxt, jc + SCH);
 #pragma unroll
                 for (int q = 0; q < SCH; ++q) {
@@ -1803,24 +1927,21 @@ struct Solver {   // SCH: chunk (columns / rows) streamed per step group; RTN: n
                     }
                 }
                 shift();
-            };
-            if constexpr (RTN) {
-                // with a run-time n the compiler unrolled this loop once per possible
-                // remainder (248 VGPRs, stack reloads inside the sweep: c5's mixed
-                // horizons); rolled it stays one chunk body
-#pragma unroll 1
-                for (int jc = 64 * T; jc < jend; jc += SCH) chunk(jc);
-            } else {
-                for (int jc = 64 * T; jc < jend; jc += SCH) chunk(jc);
             }
         }
     }
     // backward over the rows owned by slot T; slots > T are final
     template <int T>
     __device__ __forceinline__ void bwd(int jlast) {
-        if constexpr (T < R) {
+        if constexpr (T < R && !RTN) {
+            constexpr int jstart = (T == R - 1) ? ((NC - 1) / SCH) * SCH : 64 * T + 64 - SCH;
+            constexpr int nch = jstart >= 64 * T ? (jstart - 64 * T) / SCH + 1 : 0;
+            bwd_chunks<T, jstart>(std::make_integer_sequence<int, nch>{});
+            if constexpr (nch > 0) flush_lane_d<0>(xf[T], blo, bhi);
+        } else if constexpr (T < R) {
             const int jstart = (T == R - 1) ? jlast : 64 * T + 64 - SCH;
-            auto chunk = [&](int jc) {
+#pragma unroll 1
+            for (int jc = jstart; jc >= 64 * T; jc -= SCH) {
                 if (jc > 0) load_rows(nxt, jc - SCH);
 #pragma unroll
                 for (int q = SCH - 1; q >= 0; --q) {
@@ -1835,12 +1956,6 @@ struct Solver {   // SCH: chunk (columns / rows) streamed per step group; RTN: n
                     }
                 }
                 shift();
-            };
-            if constexpr (RTN) {
-#pragma unroll 1
-                for (int jc = jstart; jc >= 64 * T; jc -= SCH) chunk(jc);
-            } else {
-                for (int jc = jstart; jc >= 64 * T; jc -= SCH) chunk(jc);
             }
         }
     }
@@ -1867,9 +1982,9 @@ struct Solver {   // SCH: chunk (columns / rows) streamed per step group; RTN: n
     }
 };
 
-template <int R, bool RTN, class LT>
+template <int R, int NC, class LT>
 __device__ __forceinline__ void chol_solve_r(const LT& L, const ldouble* bvec, ldouble* x) {
-    Solver<R, decltype(L.H), (LT::HGLOBAL ? kSolveChunkG : kSolveChunk), RTN> S(L.H, L.dinv, L.n, L.ld, bvec);
+    Solver<R, decltype(L.H), (LT::HGLOBAL ? kSolveChunkG : kSolveChunk), NC> S(L.H, L.dinv, L.n, L.ld, bvec);
     S.run(x);
 }
 
@@ -1879,18 +1994,24 @@ __device__ __forceinline__ void chol_solve_r(const LT& L, const ldouble* bvec, l
 // iteration, c5 117.7k -> 135k solves/s, profiles/r05_ab_c5_solve_classes.txt).
 template <int SH, class LT>
 __device__ void chol_solve(const LT& L, const ldouble* bvec, ldouble* x) {
-    constexpr bool RTN = shape_c(SH).H == 0;
+    // n of a compile-time shape (make_lay: V Hb + 1), 0 for a run-time horizon
+    constexpr int NC = shape_c(SH).H == 0 ? 0 : shape_c(SH).V * shape_c(SH).H + 1;
 #ifdef SCPQP_DIAG_X2_SOLVE   // counter attribution: the solve twice (the same x)
     for (int rep = 0; rep < 2; ++rep)
 #endif
     if (is_lead(L.lead)) {
-        const int n = L.n;
         constexpr int RM = LT::RMAX;
         lead_prio_up();
-        if (RM == 1 || n <= 64) chol_solve_r<1, RTN>(L, bvec, x);
-        else if (RM == 2 || n <= 128) chol_solve_r<(RM >= 2 ? 2 : 1), RTN>(L, bvec, x);
-        else if (RM == 3 || n <= 192) chol_solve_r<(RM >= 3 ? 3 : 1), RTN>(L, bvec, x);
-        else chol_solve_r<RM, RTN>(L, bvec, x);
+        if constexpr (NC != 0) {
+            static_assert(NC <= 64 * RM, "the layout's row slots hold the shape");
+            chol_solve_r<(NC + 63) / 64, NC>(L, bvec, x);
+        } else {
+            const int n = L.n;
+            if (RM == 1 || n <= 64) chol_solve_r<1, 0>(L, bvec, x);
+            else if (RM == 2 || n <= 128) chol_solve_r<(RM >= 2 ? 2 : 1), 0>(L, bvec, x);
+            else if (RM == 3 || n <= 192) chol_solve_r<(RM >= 3 ? 3 : 1), 0>(L, bvec, x);
+            else chol_solve_r<RM, 0>(L, bvec, x);
+        }
         lead_prio_down();
     }
     bar();

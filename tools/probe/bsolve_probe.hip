@@ -378,7 +378,7 @@ __global__ __launch_bounds__(256, 2) void probe(double* xout, long long* cyc, in
         const long long t0 = __builtin_amdgcn_s_memtime();
         for (int r = 0; r < reps; ++r) {
             if constexpr (VAR == 0) {
-                Solver<R, ldouble*, 4> S(H, dinv, n, 0, b);
+                Solver<R, ldouble*, 4, NC> S(H, dinv, n, 0, b);
                 S.run(x);
             } else if constexpr (VAR == 1) {
                 BSolver<R, 4, ldouble*> S(H, dinv, n, b);

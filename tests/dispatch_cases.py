@@ -174,3 +174,44 @@ def oracle_job(args):
         del h["A"], h["b"], h["u_lin"]
     r.lin = None
     return r, one.u, active, spread
+
+
+# The device's cold IPM iteration count of the first QP (trace slot 5 of SCP iteration 0, no
+# u_warm) may exceed the oracle's qp_ipm(init="omega") count on the same scaled QP by at most
+# this many iterations (tests/test_gpu_dispatch.py::test_cold_ipm_iteration_count): the largest
+# difference measured over every problem of every row, plus one for a stopping test evaluated
+# one rounding either side of its threshold.  Measured: +1 on one problem of 160 (3 vehicles at
+# Hp 41, problem 2: 19 against 18), otherwise 0 or below.  The table: profiles/linalg_gpu_tests.txt.
+IPM_COUNT_MARGIN = 2
+
+
+def first_qp_job(args):
+    """The scaled first QP (P, q, G, h) of one problem (oracle_jobs arguments): the QP of the
+    first SCP iteration, linearised at the problem's start, as qp_solve scales it."""
+    _paths()
+    from oracle import scp_reference as R
+    kind, n_veh, hp_max, hp, x0, u0, ec, obst = args
+    sc = scenario(kind, n_veh, hp_max)
+    p = R.make_problem(sc, x0, u0, ec, Hp=hp, obst=obst if sc.nObst else None)
+    r = R.scp_solve(p, mode="structured", keep_history=True, max_scp=1)
+    lin = R.linearise(p, "structured")
+    nV = sc.nVeh
+    N = nV * hp
+    Phi0 = np.zeros((N, N))
+    Psi0 = np.zeros(N)
+    for v in range(nV):
+        Phi0[hp * v:hp * (v + 1), hp * v:hp * (v + 1)] = lin.Phi0[v]
+        Psi0[hp * v:hp * (v + 1)] = lin.Psi0[v]
+    hh = r.history[0]
+    P, q, G, h = R.qp_matrices(Phi0, Psi0, hh["A"], hh["b"], p.u_lim)
+    return R.qp_scale(P, q, G, h, p.u_lim, N)[:4]
+
+
+def ipm_count_job(args):
+    """(iterations, status) of the oracle's qp_ipm(init="omega") on a problem's first QP."""
+    _paths()
+    from oracle import scp_reference as R
+    import scp_parity as SP
+    SP.single_thread_blas()
+    res = R.qp_ipm(*first_qp_job(args), init="omega")
+    return res[3], res[4]

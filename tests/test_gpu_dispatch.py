@@ -222,3 +222,27 @@ def test_mixed_horizons(gpu, pool, cid):
         H = int(bt.hp[b])
         assert np.all(u[b, sc.nVeh * H:] == 0.0), (cid, b)
         assert np.all(traj[b, H * 2 * sc.nVeh:] == 0.0), (cid, b)
+
+
+@pytest.mark.parametrize("cid", ALL_IDS)
+def test_cold_ipm_iteration_count(gpu, pool, cid):
+    """The IPM around the factorisation converges with an inexact Newton direction, so a
+    factor or a substitution that has lost digits shows up as more iterations, not as a wrong
+    u.  The device's cold iteration count of the first QP (trace slot 5 of SCP iteration 0, no
+    u_warm) against the oracle's qp_ipm(init="omega") on the same scaled QP, every problem of
+    the row: device <= oracle + DC.IPM_COUNT_MARGIN."""
+    c = DC.by_id(cid)
+    sc, bt = DC.case_inputs(c)
+    orc = pool.map(DC.ipm_count_job, DC.oracle_jobs(c.scenario, c.n_veh, sc, bt), chunksize=1)
+    S = solver_for(sc, bt, DC.N_PROBLEMS)
+    out = S.solve(bt.x0, bt.u0, bt.ec_noise, hp=hp_arg(c, bt, gpu), obst=obst_arg(sc, bt),
+                  max_scp_iter=1, trace=True)
+    torch.cuda.synchronize()
+    dev = [SP.device_trace(out, b, sc.nVeh, sc.nObst, int(bt.hp[b]), bt.hp_max)[0]["ipm_iters"]
+           for b in range(DC.N_PROBLEMS)]
+    S.close()
+    diff = [d - o for d, (o, _) in zip(dev, orc)]
+    print(f"ipm_count {cid}: device {dev} oracle {[o for o, _ in orc]} (status "
+          f"{[s for _, s in orc]}) device - oracle max {max(diff)} min {min(diff)}")
+    assert all(d >= 1 for d in dev), (cid, dev)
+    assert max(diff) <= DC.IPM_COUNT_MARGIN, (cid, diff)

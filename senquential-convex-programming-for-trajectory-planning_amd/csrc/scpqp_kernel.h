@@ -183,6 +183,13 @@ constexpr int kIdlSlot = 65;    // 1 / polish delta of the current polish round
 constexpr int kWorkSlot = 66;   // the problem index taken from the work queue (int)
 constexpr int kLeadSlot = 67;   // lead election (2 ints)
 constexpr int kOrSlot = 68;     // workgroup OR of the sampler's quirk flags (int)
+// The omega partial sums of a right-hand side formed beside the factorisation (GtSide: one
+// per virtual wave), red[66, 70).  They cannot live in [0, 48) like block_reduce4's: the
+// factorisation owns [0, 64) as ldbuf.  The three int slots above are dead inside a QP
+// solve (the work item and the sampler's flags are read right after the barrier that
+// publishes them and written again before the next read; the lead is elected once per
+// launch), so the partials share their storage.
+constexpr int kSidePart = 66;
 constexpr int kPivSlot = 72;    // pivots [step mod 2G][CB] (G = 4 panels per group on
                                 // workspace factors, else 1; CB = 8)
 __host__ __device__ constexpr int red_size(bool hG) { return kPivSlot + 2 * (hG ? 4 : 1) * 8; }
@@ -927,9 +934,11 @@ __device__ __noinline__ int setup_problem_ni(const cKArgs* ap, const cParams* Pp
 // all four waves share the work (one lane per output used 80 of 256 threads
 // with chains of up to Hb terms).  fn(e, sum) runs in the owner lane (s == 0).
 constexpr int kSplit = 3, kPerWave = 21, kPerPass = kPerWave * NWAVE;
+// w: the wave whose share of the outputs this wave forms; its own, unless a helper wave
+// stands in for another (GtSide).
 template <class TermSum, class Fn>
-__device__ __forceinline__ void split3_outputs(int nout, TermSum part, Fn fn) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+__device__ __forceinline__ void split3_outputs(int nout, TermSum part, Fn fn, int w) {
+    const int lane = threadIdx.x & 63;
     const int j = lane / kSplit, sidx = lane - j * kSplit;
     for (int base = 0; base < nout; base += kPerPass) {
         const int e = base + w * kPerWave + j;
@@ -939,6 +948,10 @@ __device__ __forceinline__ void split3_outputs(int nout, TermSum part, Fn fn) {
         const double x2 = __shfl_down(acc.x, 2), y2 = __shfl_down(acc.y, 2);
         if (valid && sidx == 0) fn(e, double2v{acc.x + x1 + x2, acc.y + y1 + y2});
     }
+}
+template <class TermSum, class Fn>
+__device__ __forceinline__ void split3_outputs(int nout, TermSum part, Fn fn) {
+    split3_outputs(nout, part, fn, (int)(threadIdx.x >> 6));
 }
 
 // y[v][k] = sum_{l<=k} g[v][k-l] * x[v*Hb + l]     (calB x, MPC_Iter.py:146-147)
@@ -964,7 +977,7 @@ __device__ __forceinline__ void toeplitz_apply(const LT& L, PX x, PY y) {
 
 // out(e, sum_{k>=l} g[v][k-l]' y[v][k]) for every e = v*Hb + l   (calB' y)
 template <class LT, class PY, class Fn>
-__device__ __forceinline__ void toeplitz_t_apply(const LT& L, PY y, Fn out) {
+__device__ __forceinline__ void toeplitz_t_apply(const LT& L, PY y, Fn out, int w) {
     split3_outputs(
         L.V * L.Hb,
         [&](int e, int sidx) {
@@ -976,7 +989,11 @@ __device__ __forceinline__ void toeplitz_t_apply(const LT& L, PY y, Fn out) {
                 acc += gv[(k - l) * 2] * y[yb + 2 * k] + gv[(k - l) * 2 + 1] * y[yb + 2 * k + 1];
             return double2v{acc, 0.0};
         },
-        [&](int e, double2v r) { out(e, r.x); });
+        [&](int e, double2v r) { out(e, r.x); }, w);
+}
+template <class LT, class PY, class Fn>
+__device__ __forceinline__ void toeplitz_t_apply(const LT& L, PY y, Fn out) {
+    toeplitz_t_apply(L, y, out, (int)(threadIdx.x >> 6));
 }
 
 // sum over the rows incident to (v, k) of coef(r) * sigma * e_r  (2-vector)
@@ -1021,22 +1038,82 @@ __device__ __forceinline__ double gx_row(const LT& L, PX xu, double xw, int r) {
 // returned (uniform).  No barrier after the u-part: the caller's next barrier publishes it.
 // BUF: the reduction's buffer (block_reduce4), chosen by the caller against the
 // reduction before it.
-template <int BUF, class LT, class PT, class Fin>
-__device__ double gt_apply_fin(const LT& L, PT t, Fin fin) {
-    const int tid = threadIdx.x;
+// The two halves of G' t, either side of its reduction, for thread vt (wave vt / 64) of the
+// workgroup: the thread itself (gt_apply_fin), or a helper wave standing in for it (GtSide).
+// Before: the incident sums of this thread's outputs into yb; returns its omega partial sum.
+template <class LT, class PT>
+__device__ __forceinline__ double gt_incident_part(const LT& L, PT t, int vt) {
     double wsum = 0.0;
-    for (int e = tid; e < L.V * L.Hb; e += NT) {
+    for (int e = vt; e < L.V * L.Hb; e += NT) {
         const int v = e / L.Hb, k = e % L.Hb;
         double s0, s1;
         incident_sum(L, v, k, [&](int r) { return t[r]; }, s0, s1);
         L.yb[2 * e] = s0;
         L.yb[2 * e + 1] = s1;
     }
-    for (int r = tid; r < L.m; r += NT) wsum += t[r] * L.rowW[r];
+    for (int r = vt; r < L.m; r += NT) wsum += t[r] * L.rowW[r];
+    return wsum;
+}
+// After (yb published): calB' yb and the bound rows, fin(e, .) in the lane that owns e.
+template <class LT, class PT, class Fin>
+__device__ __forceinline__ void gt_toeplitz_part(const LT& L, PT t, Fin fin, int vw) {
+    toeplitz_t_apply(L, L.yb, [&](int e, double tt) { fin(e, tt + t[L.m + e] - t[L.m + L.N + e]); }, vw);
+}
+template <int BUF, class LT, class PT, class Fin>
+__device__ double gt_apply_fin(const LT& L, PT t, Fin fin) {
+    const int tid = threadIdx.x;
+    const double wsum = gt_incident_part(L, t, tid);
     double red[4] = {wsum, 0.0, 0.0, 0.0};
     block_reduce4<1, BUF>(red, 0, L.red);   // barrier: yb visible afterwards
-    toeplitz_t_apply(L, L.yb, [&](int e, double tt) { fin(e, tt + t[L.m + e] - t[L.m + L.N + e]); });
+    gt_toeplitz_part(L, t, fin, tid >> 6);
     return red[0] - t[L.mc - 1];
+}
+
+// G' t beside the factorisation (cholesky's side job): the non-lead waves, idle at panel
+// step 0 and early at the barrier from step 1 on, form it in two stages with panel barriers
+// between them, which stand in for gt_apply_fin's reduction barrier:
+//   stage 0  incident sums -> yb, each virtual wave's omega partial -> red[kSidePart + vw]
+//   stage 1  calB' yb and the bound rows -> fin; the omega entry -> finw (virtual thread 0)
+// Helper h of nh takes the shares of the workgroup's waves vw = h, h + nh, ... < NWAVE as
+// virtual threads vt = 64 vw + lane, so every row, output and lane of the split keeps the
+// place gt_apply_fin gives it, and the partials are summed in block_reduce4's order
+// (wave_sum per wave, then ((p0 + p1) + p2) + p3): every stored value is bitwise
+// gt_apply_fin's.  Nothing here goes through block_reduce4's buffers, so the hidden
+// reduction is outside the buffer rule that SCPQP_DIAG_REDUCE_CHECK counts: its partials
+// are written in stage 0 and read in stage 1 only, a panel barrier apart, and a
+// factorisation's remaining barriers lie before the next stage 0.
+// t, yb, rowE, rowW, g and whatever fin touches must be disjoint from the factorisation's
+// storage (H, dinv, red[0, 64), the failure flag and the pivots): true of tv (its own
+// vector, or pb's storage), rhs, rd, qs and dz in every plan (plan_offsets).
+template <class LT, class PT, class Fin, class FinW>
+struct GtSide {
+    static constexpr int STAGES = 2;
+    const LT& L;
+    PT t;
+    Fin fin;
+    FinW finw;
+    __device__ __forceinline__ void operator()(int stage, int h, int nh) const {
+        const int lane = threadIdx.x & 63;
+        ldouble* part = L.red + kSidePart;
+        for (int vw = h; vw < NWAVE; vw += nh) {
+            if (stage == 0) {
+                const double ws = wave_sum(gt_incident_part(L, t, vw * 64 + lane));
+                if (lane == 0) part[vw] = ws;
+            } else {
+                gt_toeplitz_part(L, t, fin, vw);
+                if (vw == 0 && lane == 0) {
+                    double r = part[0];
+#pragma unroll
+                    for (int ww = 1; ww < NWAVE; ++ww) r = r + part[ww];
+                    finw(r - t[L.mc - 1]);
+                }
+            }
+        }
+    }
+};
+template <class LT, class PT, class Fin, class FinW>
+__device__ __forceinline__ GtSide<LT, PT, Fin, FinW> gt_side(const LT& L, PT t, Fin fin, FinW finw) {
+    return GtSide<LT, PT, Fin, FinW>{L, t, fin, finw};
 }
 
 // ---------------------------------------------------------------------------
@@ -1316,7 +1393,7 @@ __device__ __forceinline__ void lead_prio_down() { __builtin_amdgcn_s_setprio(0)
 //    (p_ic -= (p_ic' / D_c') U_cc', U = L D unscaled), which for the block's own rows
 //    repeats the uniform factorisation operation for operation.
 template <int RS, bool OPQ, class HP>
-__device__ __forceinline__ void panel_factor(HP H, ldouble* dinv, int n, int r0, int jb, int jp,
+__device__ __forceinline__ int panel_factor(HP H, ldouble* dinv, int n, int r0, int jb, int jp,
                                               const ldouble* dprev, ldouble* dout, lint* flag,
                                               int nprev, ldouble* ldbuf) {
     // OPQ (kernels with more than two row slots, c3): the lane index through an empty
@@ -1423,12 +1500,13 @@ __device__ __forceinline__ void panel_factor(HP H, ldouble* dinv, int n, int r0,
         // is implicit), so the 8 x 8 block factorisation, the row substitution and the
         // stores are skipped; D and 1/D are the values they would produce.
         const double D = readlane_d(p[0][0], 0);
+        const int bad1 = !(D > 0.0) || !isfinite(D);
         if (lane == 0) {
             dinv[r0] = recip(D);
             dout[0] = D;
-            flag[0] = !(D > 0.0) || !isfinite(D);
+            flag[0] = bad1;
         }
-        return;
+        return bad1;
     }
     double inv[CB], dg[CB];
     int bad = 0;
@@ -1500,6 +1578,7 @@ __device__ __forceinline__ void panel_factor(HP H, ldouble* dinv, int n, int r0,
     }
     if (lane == 0) flag[0] = bad;
     PROF_ACC_FINE(21);
+    return bad;   // formed from broadcast values: the same in every lane, and what flag[0] holds
 }
 
 // Rank-CB update of panel j0 (pivots dcur) on rows/columns >= r1, by threads
@@ -1658,9 +1737,110 @@ __device__ __forceinline__ void trailing_update_mfma(HP H, int n, int j0, int r1
 constexpr int kGroup = 4;
 static_assert(kPivSlot + 2 * kGroup * CB == red_size(true) && kPivSlot + 2 * CB == red_size(false),
               "the pivot buffer of red_size");
+static_assert(kSidePart > kIdlSlot && kSidePart + NWAVE <= kPivSlot,
+              "the side job's partials lie between the polish slot and the pivots");
 
-template <class LT>
-__device__ bool cholesky(const LT& L) {
+// Side job of the factorisation: work that does not need the factor, run by the non-lead
+// waves in Side::STAGES stages, each at a panel step of its own (side_step) before their
+// trailing update.  The panel barriers that are there anyway order the stages and publish
+// the result, the last stage's at the latest by the factorisation's last barrier.
+// On an early failure the later stages do not run: the caller abandons the solve.
+// Only where the lead's panel chain bounds the step and the steps suffice (side_fits);
+// elsewhere the caller keeps the job in front of the factorisation.
+struct NoSide {
+    static constexpr int STAGES = 0;
+    __device__ __forceinline__ void operator()(int, int, int) const {}
+};
+template <int STAGES, class LT>
+__device__ __forceinline__ bool side_fits(const LT& L) {
+    // LDS factors only: on a workspace factor the tile waves are the critical path
+    return !LT::HGLOBAL && L.n > (STAGES - 1) * CB;
+}
+// The panel step of stage k: stage 0 at step 0, where the other waves have no trailing
+// update yet; the later stages from step kSideLate on, one step each, or on the last steps
+// of a factorisation that has fewer.  At step 1 the trailing update is at its largest and
+// the other waves reach the barrier only shortly before the lead: a second stage there or at
+// step 4 made the lead wait for them (its barrier wait at B = 1: 1.0k cycles per IPM
+// iteration without a side job, 3.7k with the stage at step 2, 2.8k at 4, 1.8k at 6 and 8;
+// DESIGN §3).  The update shrinks with every step.  -DSCPQP_SIDE_LATE=k moves it (A/B builds).
+#ifndef SCPQP_SIDE_LATE
+#define SCPQP_SIDE_LATE 8
+#endif
+constexpr int kSideLate = SCPQP_SIDE_LATE;
+template <int STAGES>
+__host__ __device__ constexpr int side_step(int k, int nsteps) {
+    // not the last step where an earlier one is free: the last panel of n = 8 j + 1 is
+    // the omega row alone, the lead's shortest step
+    const int late = kSideLate + k - 1, last = nsteps - STAGES + k - (nsteps > STAGES ? 1 : 0);
+    return k == 0 ? 0 : (late < last ? late : last);
+}
+
+// The factorisation of an LDS factor with a side job.  The lead and the other waves run
+// loops of their own over the same panel steps: each wave meets the same barriers in the
+// same order (a barrier counts the workgroup's waves, wherever in the code each arrives),
+// both loops leave on the same failure flag, and the lead's loop holds the panel chain
+// alone, so the side job costs its registers and its schedule nothing.
+template <class LT, class Side>
+__device__ __forceinline__ bool cholesky_side(const LT& L, const Side& side) {
+    static_assert(!LT::HGLOBAL, "side jobs run beside LDS factors only");
+    const int n = __builtin_amdgcn_readfirstlane(L.n);
+    constexpr int RS = LT::RMAX;
+    lint* flag = (lint*)(L.red + kRedFlag);
+    ldouble* ldbuf = L.red;
+    ldouble* dbuf = L.red + kPivSlot;
+    const int nsteps = (n + CB - 1) / CB;
+    PROF_T0();
+    if (is_lead(L.lead)) {
+#pragma nounroll   // and no peeling of step 0: one copy of the panel code
+        for (int r0 = 0, s = 0; r0 < n; r0 += CB, ++s) {
+            const int par = s & 1;
+            const int jb = min(CB, n - r0), jp = r0 - CB;
+            const ldouble* dprev = dbuf + ((s - 1) & 1) * CB;
+            ldouble* dn = dbuf + par * CB;
+            int bad;
+            lead_prio_up();
+            if (RS == 1 || n - r0 <= 64) bad = panel_factor<1, false>(L.H, L.dinv, n, r0, jb, jp, dprev, dn, flag + par, 1, ldbuf);
+            else bad = panel_factor<RS, (RS > 2)>(L.H, L.dinv, n, r0, jb, jp, dprev, dn, flag + par, 1, ldbuf);
+            lead_prio_down();
+#if defined(SCPQP_PROF) && defined(SCPQP_PROF_FINE)
+            unsigned long long _pb = __builtin_amdgcn_s_memtime();
+#endif
+            bar();
+#if defined(SCPQP_PROF) && defined(SCPQP_PROF_FINE)
+            if ((threadIdx.x & 63) == 0) atomicAdd(&g_prof[22], __builtin_amdgcn_s_memtime() - _pb);
+#endif
+            // the lead holds the flag it wrote: no LDS round trip between its panels (the
+            // other waves read flag[par]: the same value, so the return stays uniform)
+            if (__builtin_amdgcn_readfirstlane(bad)) return false;
+        }
+    } else {
+        const int tw = (wave_id() - L.lead + NWAVE - 1) % NWAVE;   // 0 .. NWAVE-2
+#pragma nounroll
+        for (int r0 = 0, s = 0; r0 < n; r0 += CB, ++s) {
+            const int par = s & 1;
+            const int jb = min(CB, n - r0), r1 = r0 + jb, jp = r0 - CB;
+            const ldouble* dprev = dbuf + ((s - 1) & 1) * CB;
+#pragma unroll
+            for (int k = 0; k < Side::STAGES; ++k)
+                if (s == side_step<Side::STAGES>(k, nsteps)) side(k, tw, NWAVE - 1);
+            if (jp >= 0) trailing_update(L.H, n, jp, r1, dprev, tw * 64 + (int)(threadIdx.x & 63), NT - 64);
+#if defined(SCPQP_PROF) && defined(SCPQP_PROF_FINE)
+            unsigned long long _pb = __builtin_amdgcn_s_memtime();
+#endif
+            bar();
+#if defined(SCPQP_PROF) && defined(SCPQP_PROF_FINE)
+            if (threadIdx.x == 64 * ((L.lead + 1) & 3)) atomicAdd(&g_prof[23], __builtin_amdgcn_s_memtime() - _pb);
+#endif
+            if (flag[par]) return false;
+        }
+    }
+    PROF_ACC(13);
+    return true;
+}
+
+template <class LT, class Side = NoSide>
+__device__ bool cholesky(const LT& L, const Side& side = Side{}) {
+    if constexpr (Side::STAGES > 0) return cholesky_side(L, side);
     const int n = __builtin_amdgcn_readfirstlane(L.n);
     constexpr int RS = LT::RMAX;   // row slots per lane in the panel
     constexpr int G = LT::HGLOBAL ? kGroup : 1;
@@ -2456,6 +2636,26 @@ __device__ __forceinline__ void rhs_from_tv_body(const cParams& P, const LT& L, 
     if (threadIdx.x == 0) L.rhs[L.N] = ow - P.slackW + rho * L.dz[L.N];
     bar();
 }
+// The same right-hand side as the factorisation's side job (GtSide): the caller's
+// cholesky(L, .) forms it on the non-lead waves and publishes it with its barriers.
+template <class LT>
+__device__ __forceinline__ auto rhs_from_tv_side(const cParams& P, const LT& L, double rho) {
+    return gt_side(
+        L, L.tv, [&L, rho](int e, double g) { L.rhs[e] = g - L.qs[e] + rho * L.dz[e]; },
+        [&L, &P, rho](double ow) { L.rhs[L.N] = ow - P.slackW + rho * L.dz[L.N]; });
+}
+// The right-hand sides that do not need the factor are formed beside the factorisation
+// (cholesky's side job) wherever the plan allows it (side_fits).  -DSCPQP_DIAG_RHS_FRONT
+// keeps them in front of it, on all four waves: the bitwise reference for the overlap.
+#ifdef SCPQP_DIAG_RHS_FRONT
+constexpr bool kRhsOverlap = false;
+#else
+constexpr bool kRhsOverlap = true;
+#endif
+// a phase with the order as a last template argument (the test harness builds both)
+#define PHASE_OVL                                                                     \
+    template <bool HG, bool VG, int RM, int OCC, int SH, bool OVL = kRhsOverlap && !HG> \
+    __device__ __noinline__
 PHASE void ph_rhs_from_tv(Ctx c, double rho) {
     LAYDEF;
     rhs_from_tv_body(P, L, rho);
@@ -2541,6 +2741,14 @@ __device__ __forceinline__ void newton_rhs_body(const LT& L, RW& A, int corr, do
     if (threadIdx.x == 0) L.rhs[L.N] = -L.rd[L.N] - ow;
     bar();
 }
+// The predictor's right-hand side (newton_rhs_body<false>: tv already formed) as the
+// factorisation's side job (GtSide).
+template <class LT>
+__device__ __forceinline__ auto newton_rhs_side(const LT& L) {
+    return gt_side(
+        L, L.tv, [&L](int e, double g) { L.rhs[e] = -L.rd[e] - g; },
+        [&L](double ow) { L.rhs[L.N] = -L.rd[L.N] - ow; });
+}
 // ds = -rp - G dz row by row in the thread that forms (G dz)_r, and this thread's
 // partial step lengths {primal: min over ds < 0 of -s/ds, dual: min over dl < 0 of
 // -lam/dl} from the values it just formed (round 5: one barrier and one pass over the
@@ -2611,37 +2819,76 @@ __device__ __forceinline__ void update_body(const LT& L, RW& A, double eta, doub
 // (tools/ipm_corrector_study.py, from the round-3 start): cold IPM iterations per QP
 // c2 12.5 -> 11.5, 4 veh Hp 10 10.1 -> 7.8, parallel5 18.0 -> 16.6, frog 14.7 -> 12.0.
 __device__ __forceinline__ double step_factor(double mu) { return fmax(0.99, 1.0 - mu); }
-// d = lam / s, K = P + G' diag(d) G, the predictor right-hand side (rc = s lam; it does
-// not need the factor, so it is formed before the factorisation) and L D L' of K in one
-// call (one call fewer per IPM iteration than assembly and factorisation apart: c2 +0.8 %,
-// profiles/r03_ab_fuse_fact.txt).  1 = factored.
+// the polish's tv = mask (h / delta - y), each row in its own thread (A holds sa and la)
+template <class LT, class RW>
+__device__ __forceinline__ void polish_tv_pass(const LT& L, RW& A) {
+    const double idl = L.red[kIdlSlot];
+    each_row(A, L.mc, [&](int k, int r) { L.tv[r] = A.sa(k, r) * (hval(L, r) * idl - A.la(k, r)); });
+}
+// d = lam / s, K = P + G' diag(d) G, the predictor right-hand side (rc = s lam) and
+// L D L' of K in one call (one call fewer per IPM iteration than assembly and factorisation
+// apart: c2 +0.8 %, profiles/r03_ab_fuse_fact.txt).  1 = factored.
+// The right-hand side does not need the factor: with OVL the non-lead waves form it beside
+// the factorisation (cholesky's side job), else, and where the plan has no room for that
+// (side_fits), all four waves form it in front.  On a failed factorisation it may be
+// unfinished: the caller leaves the IPM loop.
 // d and tv come from the residuals of this iterate (residuals()), which every IPM
 // iteration computes last and every IPM pass first.
-PHASE int ph_scale_assemble_rhs_factor(Ctx c) {
+PHASE_OVL int ph_scale_assemble_rhs_factor(Ctx c) {
     LAYDEF;
     PROF_T0_FINE();
     assemble(P, L, L.dd, 0.0);
     PROF_ACC_FINE0(29);
+    if constexpr (OVL) {
+        if (side_fits<2>(L)) return cholesky(L, newton_rhs_side(L)) ? 1 : 0;
+    }
     RowsMem<Lay<HG, VG, RM, OCC>> A{L};   // unused: the predictor's tv is already formed
     newton_rhs_body<false>(L, A, 0, 0.0);
     PROF_ACC_FINE0(28);
     return cholesky(L) ? 1 : 0;
 }
-// polish: K = P + rho I + G_A' G_A / delta, factored in the same call
-PHASE int ph_assemble_factor(Ctx c, double rho) {
+// polish: K = P + rho I + G_A' G_A / delta, factored in the same call.  With OVL also the
+// round's right-hand side (ph_polish_rhs, which then serves only the rounds that keep their
+// factor): tv first, each row in its own thread and published by the assembly's barriers,
+// the rest beside the factorisation, or after it where the plan has no room (side_fits).
+PHASE_OVL int ph_assemble_factor(Ctx c, double rho) {
     LAYDEF;
-    assemble(P, L, L.dd, rho);
-    return cholesky(L) ? 1 : 0;
+    if constexpr (OVL) {
+        {
+            ROWSDEF;
+            A.template load<RV_SA | RV_LA>();
+            polish_tv_pass(L, A);
+        }
+        assemble(P, L, L.dd, rho);
+        if (side_fits<2>(L)) return cholesky(L, rhs_from_tv_side(P, L, P.polRho)) ? 1 : 0;
+        if (!cholesky(L)) return 0;
+        rhs_from_tv_body(P, L, P.polRho);
+        return 1;
+    } else {
+        assemble(P, L, L.dd, rho);
+        return cholesky(L) ? 1 : 0;
+    }
 }
 // the cold IPM's starting system P + G'G with its omega row decoupled (row N = e_N),
-// assembled and factored in one call
-PHASE void ph_init_assemble_factor(Ctx c) {
+// assembled and factored in one call; with OVL also its right-hand side -q + G'h
+// (ph_rhs_from_tv at rho = 0; tv = h and dz = 0 from ph_init_a), as in ph_assemble_factor
+PHASE_OVL void ph_init_assemble_factor(Ctx c) {
     LAYDEF;
     assemble(P, L, L.dd, 0.0);
     const int N = L.N, o = roff(N);
     for (int e = threadIdx.x; e <= N; e += NT) L.H[o + e] = e == N ? 1.0 : 0.0;
     bar();
-    cholesky(L);   // P + G'G is positive definite (box and omega rows)
+    // P + G'G is positive definite (box and omega rows)
+    if constexpr (OVL) {
+        if (side_fits<2>(L)) {
+            cholesky(L, rhs_from_tv_side(P, L, 0.0));
+        } else {
+            cholesky(L);
+            rhs_from_tv_body(P, L, 0.0);
+        }
+    } else {
+        cholesky(L);
+    }
 }
 // predictor back-substitution, affine step and centring, corrector right-hand side
 PHASE double ph_back_affine_rhs(Ctx c, double mu) {
@@ -2705,8 +2952,7 @@ PHASE D4 ph_scales(Ctx c) {
 // polish right-hand side: tv = mask (h / delta - y), rhs = -q + G' tv + rho x_k
 template <class LT, class RW>
 __device__ __forceinline__ void polish_rhs_body(const cParams& P, const LT& L, RW& A) {
-    const double idl = L.red[kIdlSlot];
-    each_row(A, L.mc, [&](int k, int r) { L.tv[r] = A.sa(k, r) * (hval(L, r) * idl - A.la(k, r)); });
+    polish_tv_pass(L, A);
     bar();
     rhs_from_tv_body(P, L, P.polRho);
 }
@@ -2902,7 +3148,8 @@ __device__ __forceinline__ bool polish_rounds(Ctx c, double hmax, double rho, in
             if (!fact) break;
         }
         int conv = 0;
-        PH(ph_polish_rhs)(c);
+        // a refactoring round's right-hand side came with its factor (ph_assemble_factor)
+        if (!(kRhsOverlap && !HG) || !refactor) PH(ph_polish_rhs)(c);
         for (int ref = 0; ref < cap; ++ref) {
             PH(ph_solve)(c, 1);
             const D4 d = PH(ph_polish_dual_next)(c, ref, cap, early);
@@ -2958,7 +3205,7 @@ __device__ __forceinline__ bool qp_solve_body(Ctx c, const QpKnobs& K, int& qfla
     PROF_T0();
     PH(ph_init_a)(c);
     PH(ph_init_assemble_factor)(c);
-    PH(ph_rhs_from_tv)(c, 0.0);
+    if constexpr (!(kRhsOverlap && !HG)) PH(ph_rhs_from_tv)(c, 0.0);
     PH(ph_solve)(c, 0);
     PH(ph_init_b)(c);
     PROF_ACC(16);

@@ -97,9 +97,12 @@ def rhs(K, tag):
 # ---------------------------------------------------------------------------------------
 # family (b)
 # ---------------------------------------------------------------------------------------
-def ipm_systems(P, q, G, h, tol=None, maxit=60):
+def ipm_systems(P, q, G, h, tol=None, maxit=60, iterates=None):
     """qp_ipm(init='omega') of the oracle, restated as tools/polish_reuse_study.py does, that
-    also returns the normal matrix of every iteration: (x, s, lam, iterations, status, [K])."""
+    also returns the normal matrix of every iteration: (x, s, lam, iterations, status, [K]).
+    ``iterates``: a list that receives, per iteration that factors, a dict of the iterate
+    (x s lam rd rp mu), the affine direction (dx_aff ds_aff dl_aff), sigma mu (smu), the
+    corrected direction (dx ds dl) and the damped steps (eta ap ad); tests/qp_phase_cases.py."""
     from oracle import scp_reference as R
     import scipy.linalg
     tol = R.IPM_TOL if tol is None else tol
@@ -132,10 +135,14 @@ def ipm_systems(P, q, G, h, tol=None, maxit=60):
         dx, ds, dl = solve(s * lam)
         a = R._max_step(s, ds, lam, dl)
         sigma = ((s + a * ds) @ (lam + a * dl) / mc / mu) ** 3
+        aff = (dx, ds, dl)
         dx, ds, dl = solve(s * lam + ds * dl - sigma * mu)
         eta = max(0.99, 1.0 - mu)
         ap = min(1.0, eta * R._max_step(s, ds, np.ones_like(lam), np.zeros_like(dl)))
         ad = min(1.0, eta * R._max_step(np.ones_like(s), np.zeros_like(ds), lam, dl))
+        if iterates is not None:
+            iterates.append(dict(x=x, s=s, lam=lam, rd=rd, rp=rp, mu=mu, dx_aff=aff[0], ds_aff=aff[1],
+                                 dl_aff=aff[2], smu=sigma * mu, dx=dx, ds=ds, dl=dl, eta=eta, ap=ap, ad=ad))
         x = x + ap * dx
         s = s + ap * ds
         lam = lam + ad * dl

@@ -1767,11 +1767,21 @@ __device__ __forceinline__ bool side_fits(const LT& L) {
 #define SCPQP_SIDE_LATE 8
 #endif
 constexpr int kSideLate = SCPQP_SIDE_LATE;
+// Where the first solve's forward sweep follows the right-hand side (FwdSide), the later
+// stages start at step kFwdSideLate = 6 instead: the sweep runs in the steps behind them, and
+// from step 8 that leaves n = 81 two steps of 40 columns each, which outlast the lead's
+// panel (its barrier wait at B = 1, fine stamps: 1.9k cycles per IPM iteration without the
+// sweep, 4.2k with the stage at 8, 2.2k at 6 with four steps of 20 columns).
+// -DSCPQP_FWD_SIDE_LATE=k moves it (A/B builds).
+#ifndef SCPQP_FWD_SIDE_LATE
+#define SCPQP_FWD_SIDE_LATE 6
+#endif
+constexpr int kFwdSideLate = SCPQP_FWD_SIDE_LATE;
 template <int STAGES>
-__host__ __device__ constexpr int side_step(int k, int nsteps) {
+__host__ __device__ constexpr int side_step(int k, int nsteps, int late0 = kSideLate) {
     // not the last step where an earlier one is free: the last panel of n = 8 j + 1 is
     // the omega row alone, the lead's shortest step
-    const int late = kSideLate + k - 1, last = nsteps - STAGES + k - (nsteps > STAGES ? 1 : 0);
+    const int late = late0 + k - 1, last = nsteps - STAGES + k - (nsteps > STAGES ? 1 : 0);
     return k == 0 ? 0 : (late < last ? late : last);
 }
 
@@ -1780,8 +1790,47 @@ __host__ __device__ constexpr int side_step(int k, int nsteps) {
 // same order (a barrier counts the workgroup's waves, wherever in the code each arrives),
 // both loops leave on the same failure flag, and the lead's loop holds the panel chain
 // alone, so the side job costs its registers and its schedule nothing.
-template <class LT, class Side>
-__device__ __forceinline__ bool cholesky_side(const LT& L, const Side& side) {
+// The first solve's forward sweep as a further side job (FwdSide, below the Solver): helper
+// kFwdHelper alone runs its share of step s in its own step loop, before its trailing
+// update.  It is the last helper: trailing_update deals the tiles to the helpers' threads
+// in order, so in the late steps, where fewer than 128 tiles are left (n = 81: from step 6
+// on), it has none, and at no step more than another helper.
+struct NoFwd {
+    static constexpr bool ON = false;
+    __device__ __forceinline__ void operator()(int) const {}
+};
+constexpr int kFwdHelper = NWAVE - 2;
+constexpr int kSolveChunk = 4;    // chunk (columns / rows) of a factor in LDS that the solves stream per step group
+// The sweep's schedule: fwd_sched(s, nsteps, n, s1) columns are done after panel step s, so
+// step s covers [fwd_sched(s - 1, ..), fwd_sched(s, ..)).  s1 is the step whose barrier
+// publishes the right-hand side (side_step of the last stage): nothing runs before step
+// s1 + 1.  At step s only the panels < s are final, CB s columns.  What is left is spread
+// evenly over the steps that are left, in whole chunks of the solve, so that no step's
+// share outlasts the lead's panel; the last step ends at column n - 1 (L is unit lower: row
+// n - 1 needs no step of its own).
+__host__ __device__ constexpr int fwd_sched(int s, int nsteps, int n, int s1) {
+    int j = 0;
+    for (int t = s1 + 1; t <= s && t < nsteps; ++t) {
+        const int left = n - 1 - j, steps = nsteps - t;
+        const int share = ((left + steps - 1) / steps + kSolveChunk - 1) / kSolveChunk * kSolveChunk;
+        int e = j + share;
+        if (e > CB * t) e = CB * t;
+        if (e > n - 1) e = n - 1;
+        j = e;
+    }
+    return j;
+}
+// Whether it fits: whole chunks, at least kFwdMinSteps panel steps after the right-hand side's
+// (one step would be the whole sweep beside the lead's shortest panel: n = 41 has 6 steps,
+// the stage at step 4), and the last step reaches column n - 1.
+constexpr int kFwdMinSteps = 2;
+__host__ __device__ constexpr bool fwd_sched_fits(int nsteps, int n, int s1) {
+    return n > 1 && (n - 1) % kSolveChunk == 0 && nsteps == (n + CB - 1) / CB && s1 >= 0 &&
+           nsteps - 1 - s1 >= kFwdMinSteps && fwd_sched(nsteps - 1, nsteps, n, s1) == n - 1;
+}
+
+template <class LT, class Side, class Fwd = NoFwd>
+__device__ __forceinline__ bool cholesky_side(const LT& L, const Side& side, const Fwd& fwd = Fwd{}) {
     static_assert(!LT::HGLOBAL, "side jobs run beside LDS factors only");
     const int n = __builtin_amdgcn_readfirstlane(L.n);
     constexpr int RS = LT::RMAX;
@@ -1822,7 +1871,10 @@ __device__ __forceinline__ bool cholesky_side(const LT& L, const Side& side) {
             const ldouble* dprev = dbuf + ((s - 1) & 1) * CB;
 #pragma unroll
             for (int k = 0; k < Side::STAGES; ++k)
-                if (s == side_step<Side::STAGES>(k, nsteps)) side(k, tw, NWAVE - 1);
+                if (s == side_step<Side::STAGES>(k, nsteps, Fwd::ON ? kFwdSideLate : kSideLate)) side(k, tw, NWAVE - 1);
+            if constexpr (Fwd::ON) {
+                if (tw == kFwdHelper) fwd(s);
+            }
             if (jp >= 0) trailing_update(L.H, n, jp, r1, dprev, tw * 64 + (int)(threadIdx.x & 63), NT - 64);
 #if defined(SCPQP_PROF) && defined(SCPQP_PROF_FINE)
             unsigned long long _pb = __builtin_amdgcn_s_memtime();
@@ -1838,9 +1890,10 @@ __device__ __forceinline__ bool cholesky_side(const LT& L, const Side& side) {
     return true;
 }
 
-template <class LT, class Side = NoSide>
-__device__ bool cholesky(const LT& L, const Side& side = Side{}) {
-    if constexpr (Side::STAGES > 0) return cholesky_side(L, side);
+template <class LT, class Side = NoSide, class Fwd = NoFwd>
+__device__ bool cholesky(const LT& L, const Side& side = Side{}, const Fwd& fwd = Fwd{}) {
+    static_assert(!Fwd::ON || Side::STAGES > 0, "the sweep follows the side job's right-hand side");
+    if constexpr (Side::STAGES > 0) return cholesky_side(L, side, fwd);
     const int n = __builtin_amdgcn_readfirstlane(L.n);
     constexpr int RS = LT::RMAX;   // row slots per lane in the panel
     constexpr int G = LT::HGLOBAL ? kGroup : 1;
@@ -1916,7 +1969,6 @@ __device__ bool cholesky(const LT& L, const Side& side = Side{}) {
 // inside the kernel, the second is slower.)
 // ---------------------------------------------------------------------------
 
-constexpr int kSolveChunk = 4;    // chunk of a factor in LDS
 constexpr int kSolveChunkG = 8;   // chunk of a factor in the workspace: twice the steps cover the L2 latency
 // One substitution step's lane traffic as a single asm statement, lanes immediate (no M0, no
 // lane mask, no select): the broadcast of lane LN of v (returned, uniform; its halves also
@@ -2160,6 +2212,74 @@ struct Solver {   // SCH: chunk (columns / rows) streamed per step group; NC: n 
             if (ii[t] < n) x[ii[t]] = xf[t];
         PROF_ACC(15);
     }
+    // --- the forward sweep over the columns [J0, J1) only (n a compile-time constant): the
+    // piece of fwd<0..3>() that a helper wave runs behind the panels of the factorisation
+    // (FwdSide).  The same fold, the same operations in the same order on r[] and the same
+    // capture; what differs is data movement only: a range loads its own first chunk, its
+    // first step has no broadcast before it to capture, and its last one is flushed.
+    // Between two ranges the state is parked in yv (fwd_range), not held in registers: the
+    // helper's trailing update runs between them, and the phase's register count is the
+    // lead's to set.  A range reads no column >= J1: the prefetch stops at J1 (ranges are whole
+    // chunks), and what a final row reads past its end is, as in run(), never used.
+    template <int T, int A, int B, int J, int Q>
+    __device__ __forceinline__ void fwd_rstep() {
+        if constexpr (J < B) {
+            const double xj = bcast_capture_d<(J & 63), (J == A ? -1 : ((J - 1) & 63))>(r[T], xf[T], blo, bhi);
+            r[T] -= cur[T][Q] * xj;
+#pragma unroll
+            for (int t = T + 1; t < R; ++t) r[t] -= cur[t][Q] * xj;
+        }
+    }
+    template <int T, int A, int B, int J1, int JC, int... Q>
+    __device__ __forceinline__ void fwd_rchunk(std::integer_sequence<int, Q...>) {
+        if constexpr (JC + SCH < J1) load_cols(nxt, JC + SCH);
+        (fwd_rstep<T, A, B, JC + Q, Q>(), ...);
+        if constexpr (JC + SCH < J1) shift();
+    }
+    template <int T, int A, int B, int J1, int... C>
+    __device__ __forceinline__ void fwd_rchunks(std::integer_sequence<int, C...>) {
+        (fwd_rchunk<T, A, B, J1, A + SCH * C>(std::make_integer_sequence<int, SCH>{}), ...);
+    }
+    // the columns of [J0, J1) that slot T owns
+    template <int T, int J0, int J1>
+    __device__ __forceinline__ void fwd_rslot() {
+        constexpr int A = J0 > 64 * T ? J0 : 64 * T, B = J1 < 64 * (T + 1) ? J1 : 64 * (T + 1);
+        if constexpr (T < R && A < B) {
+            fwd_rchunks<T, A, B, J1>(std::make_integer_sequence<int, (B - A) / SCH>{});
+            flush_lane_d<((B - 1) & 63)>(xf[T], blo, bhi);
+        }
+    }
+    // Columns [J0, J1) of L y = b.  The constructor's bvec is b for J0 == 0 and yv after
+    // that; yv holds y in the rows < J1 and the running right-hand side in the others, so
+    // after the last range, J1 = n - 1, all of y (L is unit lower: row n - 1 ends as y).
+    template <int J0, int J1>
+    __device__ __forceinline__ void fwd_range(ldouble* yv) {
+        static_assert(!RTN && J0 % SCH == 0 && J1 % SCH == 0 && 0 <= J0 && J0 < J1 && J1 < NC,
+                      "whole chunks, and no column of the last row");
+#pragma unroll
+        for (int t = 0; t < R; ++t) xf[t] = r[t];   // rows < J0: final
+        load_cols(cur, J0);
+        fwd_rslot<0, J0, J1>(); fwd_rslot<1, J0, J1>(); fwd_rslot<2, J0, J1>(); fwd_rslot<3, J0, J1>();
+#pragma unroll
+        for (int t = 0; t < R; ++t)
+            if (ii[t] < n) yv[ii[t]] = ii[t] < J1 ? xf[t] : r[t];
+    }
+    // The solve from z = D^{-1} y on, y in the constructor's bvec: run()'s second half.
+    __device__ __forceinline__ void run_back(ldouble* x) {
+        PROF_T0();
+#pragma unroll
+        for (int t = 0; t < R; ++t) {
+            r[t] = r[t] * dinv[ic[t]];
+            xf[t] = 0.0;
+        }
+        const int jlast = ((n - 1) / SCH) * SCH;
+        load_rows(cur, jlast);
+        bwd<3>(jlast); bwd<2>(jlast); bwd<1>(jlast); bwd<0>(jlast);
+#pragma unroll
+        for (int t = 0; t < R; ++t)
+            if (ii[t] < n) x[ii[t]] = xf[t];
+        PROF_ACC(15);
+    }
 };
 
 template <int R, int NC, class LT>
@@ -2192,6 +2312,85 @@ __device__ void chol_solve(const LT& L, const ldouble* bvec, ldouble* x) {
             else if (RM == 3 || n <= 192) chol_solve_r<(RM >= 3 ? 3 : 1), 0>(L, bvec, x);
             else chol_solve_r<RM, 0>(L, bvec, x);
         }
+        lead_prio_down();
+    }
+    bar();
+}
+
+// The forward sweep of the solve that follows a factorisation, hidden under it.  L y = rhs
+// uses column j of L only, final once its panel's barrier has passed, and since the
+// right-hand side is formed beside the factorisation (GtSide) it is complete by the barrier
+// of panel step s1 = side_step<2>(1, nsteps, kFwdSideLate): helper kFwdHelper runs the sweep
+// behind the panels in the steps after s1 (fwd_sched), and the lead's solve starts at
+// z = D^{-1} y (chol_solve_back).  -DSCPQP_DIAG_FWD_FRONT keeps the whole solve on the lead everywhere:
+// the bitwise reference.
+//  * No read of a column that is not final: step s covers columns < CB s only, the prefetch
+//    included (Solver::fwd_range); the lead's panel s writes columns [CB s, CB s + CB), the
+//    trailing updates columns >= CB (s + 1).
+//  * y goes to yv, the vector the solve that follows writes x to (dz after the IPM's and
+//    the polish's factor phases, z after the cold start's), never to rhs.  x's storage is
+//    dead from the right-hand side's completion to the end of the solve: the predictor's
+//    right-hand side does not read dz (-rd - G' tv) and nothing between its factor phase
+//    and its solve does; the polish's reads dz (rho x_k) in its last stage, which the
+//    barrier of step s1 ends, and the next reader (polish_dual_body) follows the solve; the
+//    cold start's reads neither z nor anything ph_init_a left there, and ph_init_b reads z
+//    as the solve's result.  After a failed factorisation yv may be unfinished, as rhs
+//    may: the IPM leaves for ph_polish_prep, which sets dz; a polish round gives up, and its
+//    caller either starts cold (ph_init_a sets dz, the cold solve z) or resumes the IPM,
+//    whose next factor phase and solve write dz before anything reads it.
+//  * It adds no barrier and sits in the helper's loop in front of its trailing update, so
+//    every wave meets the barriers it met, on the failure path too; the factorisation's
+//    last barrier publishes y.
+//  * It touches H (read), rhs (read) and yv only: not red[0, 64), the pivots, the flag or
+//    red[kSidePart ...], and goes through no reduction buffer (SCPQP_DIAG_REDUCE_CHECK).
+#ifdef SCPQP_DIAG_FWD_FRONT
+constexpr bool kFwdOverlap = false;
+#else
+constexpr bool kFwdOverlap = true;
+#endif
+// n of a compile-time shape (make_lay: V Hb + 1), 0 for a run-time horizon
+template <int SH>
+__host__ __device__ constexpr int shape_n() {
+    return shape_c(SH).H == 0 ? 0 : shape_c(SH).V * shape_c(SH).H + 1;
+}
+// LDS factors with n compiled in and room in the schedule: c2 / c4 (n = 81) and c5's n = 81
+// and n = 121 classes; n = 41, run-time shapes and workspace factors keep the solve whole
+template <bool HG, int SH>
+__host__ __device__ constexpr bool fwd_fits() {
+    constexpr int n = shape_n<SH>(), nsteps = (n + CB - 1) / CB;
+    return !HG && n != 0 && fwd_sched_fits(nsteps, n, side_step<2>(1, nsteps, kFwdSideLate));
+}
+template <int NC, class LT>
+struct FwdSide {
+    static constexpr bool ON = true;
+    static constexpr int NSTEPS = (NC + CB - 1) / CB, S1 = side_step<2>(1, NSTEPS, kFwdSideLate);
+    const LT& L;
+    ldouble* yv;
+    template <int S>
+    __device__ __forceinline__ void step(int s) const {
+        constexpr int J0 = fwd_sched(S - 1, NSTEPS, NC, S1), J1 = fwd_sched(S, NSTEPS, NC, S1);
+        if constexpr (J0 < J1) {
+            if (s == S) {
+                Solver<(NC + 63) / 64, decltype(L.H), kSolveChunk, NC> F(L.H, L.dinv, NC, L.ld, J0 == 0 ? L.rhs : yv);
+                F.template fwd_range<J0, J1>(yv);
+            }
+        }
+    }
+    template <int... S>
+    __device__ __forceinline__ void steps(int s, std::integer_sequence<int, S...>) const {
+        (step<S>(s), ...);
+    }
+    __device__ __forceinline__ void operator()(int s) const { steps(s, std::make_integer_sequence<int, NSTEPS>{}); }
+};
+// The rest of that solve: z = D^{-1} y with y in x (FwdSide's yv), the backward sweep, x.
+template <int SH, class LT>
+__device__ void chol_solve_back(const LT& L, ldouble* x) {
+    constexpr int NC = shape_n<SH>();
+    static_assert(fwd_fits<LT::HGLOBAL, SH>(), "only after a hidden forward sweep");
+    if (is_lead(L.lead)) {
+        lead_prio_up();
+        Solver<(NC + 63) / 64, decltype(L.H), kSolveChunk, NC> S(L.H, L.dinv, L.n, L.ld, x);
+        S.run_back(x);
         lead_prio_down();
     }
     bar();
@@ -2577,6 +2776,8 @@ __device__ __forceinline__ Lay<HG, VG, RM, OCC> lay_of(const Ctx& c) {
     const Lay<HG, VG, RM, OCC> L = lay_of<HG, VG, RM, OCC, SH>(cu_); \
     (void)P
 #define PH(f) f<HG, VG, RM, OCC, SH>
+// a PHASE_OVL phase as the kernel calls it: both orders spelt out
+#define PH_FWD(f) f<HG, VG, RM, OCC, SH, kRhsOverlap && !HG, kFwdSweep<HG, SH>>
 // this thread's row values of the phase (RowsReg where the shape carries them, else RowsMem)
 #define ROWSDEF RowsOf<SH, Lay<HG, VG, RM, OCC>> A{L}
 
@@ -2584,6 +2785,12 @@ __device__ __forceinline__ Lay<HG, VG, RM, OCC> lay_of(const Ctx& c) {
 PHASE void ph_solve(Ctx c, int dst) {
     LAYDEF;
     chol_solve<SH>(L, L.rhs, dst ? L.dz : L.z);
+}
+// the same solve after a factor phase that hid its forward sweep (FwdSide: y is in x's
+// storage): the lead alone, from z = D^{-1} y on
+PHASE void ph_solve_back(Ctx c, int dst) {
+    LAYDEF;
+    chol_solve_back<SH>(L, dst ? L.dz : L.z);
 }
 // mg: the obstacle margins [O][Hb] of the problem or null, passed by the kernel as an
 // argument (per lane, as Ctx) and workgroup-uniform; shapes compiled without obstacles never
@@ -2652,10 +2859,38 @@ constexpr bool kRhsOverlap = false;
 #else
 constexpr bool kRhsOverlap = true;
 #endif
-// a phase with the order as a last template argument (the test harness builds both)
+// a phase with the order as a last template argument (the test harness builds both), and
+// after it whether the helper also runs the forward sweep of the solve that follows
+// (FwdSide; only with OVL, and only where fwd_fits: the caller then continues with
+// ph_solve_back).  Off unless the caller asks: the kernel's call sites pass kFwdSweep.
 #define PHASE_OVL                                                                     \
-    template <bool HG, bool VG, int RM, int OCC, int SH, bool OVL = kRhsOverlap && !HG> \
+    template <bool HG, bool VG, int RM, int OCC, int SH, bool OVL = kRhsOverlap && !HG, \
+              bool FWD = false>                                                        \
     __device__ __noinline__
+// The helper's share of the sweep at panel step s, out of line: inlined into the factor
+// phases, the sweep's registers (the solve's two chunk buffers) were callee-saved registers
+// of the phase, which every wave, the lead too, then saved and restored around every call
+// (65 instead of 23 at c2, 264 B of stack instead of 96).  As a function of its own it
+// saves what it uses itself, on the helper alone and only in the steps that have a share.
+PHASE void ph_fwd_sweep_step(Ctx c, int s, int dst) {
+    LAYDEF;
+    FwdSide<shape_n<SH>(), Lay<HG, VG, RM, OCC>>{L, dst ? L.dz : L.z}(__builtin_amdgcn_readfirstlane(s));
+}
+// cholesky's third argument: the sweep of the solve into z (dst = 0) or dz (dst = 1)
+template <bool HG, bool VG, int RM, int OCC, int SH>
+struct FwdCall {
+    static constexpr bool ON = true;
+    static_assert(fwd_fits<HG, SH>(), "FWD only where the sweep fits");
+    Ctx c;
+    int dst;
+    __device__ __forceinline__ void operator()(int s) const {
+        if (s > FwdSide<shape_n<SH>(), Lay<HG, VG, RM, OCC>>::S1) PH(ph_fwd_sweep_step)(c, s, dst);
+    }
+};
+#define FWD_CALL(dst) FwdCall<HG, VG, RM, OCC, SH>{cu_, dst}
+// whether the kernel's factor phases hide the sweep
+template <bool HG, int SH>
+constexpr bool kFwdSweep = kFwdOverlap && kRhsOverlap && fwd_fits<HG, SH>();
 PHASE void ph_rhs_from_tv(Ctx c, double rho) {
     LAYDEF;
     rhs_from_tv_body(P, L, rho);
@@ -2839,7 +3074,9 @@ PHASE_OVL int ph_scale_assemble_rhs_factor(Ctx c) {
     PROF_T0_FINE();
     assemble(P, L, L.dd, 0.0);
     PROF_ACC_FINE0(29);
-    if constexpr (OVL) {
+    if constexpr (OVL && FWD) {
+        return cholesky(L, newton_rhs_side(L), FWD_CALL(1)) ? 1 : 0;
+    } else if constexpr (OVL) {
         if (side_fits<2>(L)) return cholesky(L, newton_rhs_side(L)) ? 1 : 0;
     }
     RowsMem<Lay<HG, VG, RM, OCC>> A{L};   // unused: the predictor's tv is already formed
@@ -2860,6 +3097,9 @@ PHASE_OVL int ph_assemble_factor(Ctx c, double rho) {
             polish_tv_pass(L, A);
         }
         assemble(P, L, L.dd, rho);
+        if constexpr (FWD) {
+            return cholesky(L, rhs_from_tv_side(P, L, P.polRho), FWD_CALL(1)) ? 1 : 0;
+        }
         if (side_fits<2>(L)) return cholesky(L, rhs_from_tv_side(P, L, P.polRho)) ? 1 : 0;
         if (!cholesky(L)) return 0;
         rhs_from_tv_body(P, L, P.polRho);
@@ -2879,7 +3119,9 @@ PHASE_OVL void ph_init_assemble_factor(Ctx c) {
     for (int e = threadIdx.x; e <= N; e += NT) L.H[o + e] = e == N ? 1.0 : 0.0;
     bar();
     // P + G'G is positive definite (box and omega rows)
-    if constexpr (OVL) {
+    if constexpr (OVL && FWD) {
+        cholesky(L, rhs_from_tv_side(P, L, 0.0), FWD_CALL(0));
+    } else if constexpr (OVL) {
         if (side_fits<2>(L)) {
             cholesky(L, rhs_from_tv_side(P, L, 0.0));
         } else {
@@ -3143,7 +3385,7 @@ __device__ __forceinline__ bool polish_rounds(Ctx c, double hmax, double rho, in
     for (int round = 0; round < max_rounds && !ok; ++round) {
         ++st.rounds;
         if (refactor) {
-            const bool fact = PH(ph_assemble_factor)(c, rho) != 0;
+            const bool fact = PH_FWD(ph_assemble_factor)(c, rho) != 0;
             PROF_ACC(7);
             if (!fact) break;
         }
@@ -3151,7 +3393,13 @@ __device__ __forceinline__ bool polish_rounds(Ctx c, double hmax, double rho, in
         // a refactoring round's right-hand side came with its factor (ph_assemble_factor)
         if (!(kRhsOverlap && !HG) || !refactor) PH(ph_polish_rhs)(c);
         for (int ref = 0; ref < cap; ++ref) {
-            PH(ph_solve)(c, 1);
+            // a refactoring round's first solve: its forward sweep came with the factor too
+            bool back = false;
+            if constexpr (kFwdSweep<HG, SH>) {
+                back = refactor && ref == 0;
+                if (back) PH(ph_solve_back)(c, 1);
+            }
+            if (!back) PH(ph_solve)(c, 1);
             const D4 d = PH(ph_polish_dual_next)(c, ref, cap, early);
             ++st.refine;
             const int stop = polish_stop(d, ref, early);
@@ -3204,9 +3452,10 @@ __device__ __forceinline__ bool qp_solve_body(Ctx c, const QpKnobs& K, int& qfla
     // s = h - Gx and lam from ph_init_b
     PROF_T0();
     PH(ph_init_a)(c);
-    PH(ph_init_assemble_factor)(c);
+    PH_FWD(ph_init_assemble_factor)(c);
     if constexpr (!(kRhsOverlap && !HG)) PH(ph_rhs_from_tv)(c, 0.0);
-    PH(ph_solve)(c, 0);
+    if constexpr (kFwdSweep<HG, SH>) PH(ph_solve_back)(c, 0);
+    else PH(ph_solve)(c, 0);
     PH(ph_init_b)(c);
     PROF_ACC(16);
     // ---- Mehrotra iterations
@@ -3223,9 +3472,10 @@ __device__ __forceinline__ bool qp_solve_body(Ctx c, const QpKnobs& K, int& qfla
                 break;
             }
             const double mu = res.c / mc;
-            if (!PH(ph_scale_assemble_rhs_factor)(c)) break;
+            if (!PH_FWD(ph_scale_assemble_rhs_factor)(c)) break;
             PROF_ACC(3);
-            PH(ph_solve)(c, 1);
+            if constexpr (kFwdSweep<HG, SH>) PH(ph_solve_back)(c, 1);
+            else PH(ph_solve)(c, 1);
             PROF_ACC(9);
             const double smu = PH(ph_back_affine_rhs)(c, mu);
             PROF_ACC(5);

@@ -684,6 +684,19 @@ __device__ __forceinline__ double mm_entry(const ldouble* A, const ldouble* B, i
     return acc;
 }
 
+// Squaring count of expm8 for the 1-norm nrm of its argument: the smallest s with
+// nrm / 2^s <= theta13 (Higham 2005, table 2.3).  A NaN or infinite norm gives 0: the
+// conversion of a non-finite double to int is undefined, and a saturated count would be
+// some 2^31 rounds of barriers for the whole workgroup; with 0 the outputs are non-finite
+// and the solve ends in SCPQP_ST_NUMERIC.  The cap lies above log2(DBL_MAX / theta13).
+constexpr int kExpmMaxSquarings = 1100;
+__host__ __device__ inline int expm_squarings(double nrm) {
+    const double theta13 = 5.371920351148152;
+    if (!(nrm > theta13) || !(nrm <= 1.7976931348623157e308)) return 0;
+    const int s = (int)ceil(log2(nrm / theta13));
+    return s < kExpmMaxSquarings ? s : kExpmMaxSquarings;
+}
+
 __device__ void expm8(ldouble* scr, bool act, ldouble* red) {
     const int lane = threadIdx.x & 63, i = lane >> 3, j = lane & 7;
     ldouble* M = scr;
@@ -699,15 +712,13 @@ __device__ void expm8(ldouble* scr, bool act, ldouble* red) {
                  b3 = 1187353796428800.0, b4 = 129060195264000.0, b5 = 10559470521600.0,
                  b6 = 670442572800.0, b7 = 33522128640.0, b8 = 1323241920.0, b9 = 40840800.0,
                  b10 = 960960.0, b11 = 16380.0, b12 = 182.0, b13 = 1.0;
-    const double theta13 = 5.371920351148152;
     double cs = 0.0;
     if (act) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) cs += fabs(M[r * 8 + j]);
     }
     const double nrm = wave_max(cs);
-    int s = 0;
-    if (nrm > theta13) s = (int)ceil(log2(nrm / theta13));
+    const int s = expm_squarings(nrm);
     if (act) A[lane] = ldexp(M[lane], -s);
     // squaring count must be uniform across the workgroup (barriers below)
     if (lane == 0) red[threadIdx.x >> 6] = act ? (double)s : 0.0;

@@ -1,8 +1,9 @@
 """ctypes binding of ``include/scpqp.h``, ``include/scpqp_noise.h``,
 ``include/scpqp_metrics.h``, ``include/scpqp_variants.h``, ``include/scpqp_truth.h``,
 ``include/scpqp_obstacles.h``, ``include/scpqp_sensing.h``, ``include/scpqp_estimator.h``,
-``include/scpqp_tracker.h``, ``include/scpqp_manoeuvres.h`` and
-``include/scpqp_tracker_accel.h`` (the C-ABI of the HIP library).
+``include/scpqp_tracker.h``, ``include/scpqp_manoeuvres.h``,
+``include/scpqp_tracker_accel.h``, ``include/scpqp_imm.h``, ``include/scpqp_margin.h`` and
+``include/scpqp_governor.h`` (the C-ABI of the HIP library).
 
 The shared library ``libscpqp.so`` is built in-tree (``__graft_entry__.build()``
 or ``python -m scpqp.build``).  There is no CPU fallback: if the library or a
@@ -273,6 +274,13 @@ IMM_EXPORTS = ("scpqp_obstacles_track_imm",)
 # every symbol include/scpqp_margin.h declares (checked by tests/test_margin_host.py)
 MARGIN_EXPORTS = ("scpqp_obstacles_margin", "scpqp_solve_margin", "scpqp_evaluate_margin")
 
+GOV_NP = 7
+(GOV_V_REF, GOV_A_ACC, GOV_A_BRAKE, GOV_K_V, GOV_J_MAX, GOV_LOOK, GOV_BAND) = range(GOV_NP)
+GOV_FIELDS = ("v_ref", "a_acc", "a_brake", "k_v", "j_max", "look", "band")
+
+# every symbol include/scpqp_governor.h declares (checked by tests/test_governor_host.py)
+GOV_EXPORTS = ("scpqp_governor_step",)
+
 _lib = None
 
 
@@ -434,6 +442,11 @@ def load(path=None):
         lib.scpqp_evaluate_margin.argtypes = [H, C.c_int32, C.POINTER(BatchIn), V, V,
                                               C.POINTER(EvalOut), V]
         lib.scpqp_evaluate_margin.restype = C.c_int
+    # likewise an A/B build from before the speed governor
+    if path is None or hasattr(lib, "scpqp_governor_step"):
+        D, I = C.c_double, C.c_int32
+        lib.scpqp_governor_step.argtypes = [I, I, I, I, D, D, V, V, V, V, V, V, V, V, V, V, V, V]
+        lib.scpqp_governor_step.restype = C.c_int
     if path is None:
         _lib = lib
     return lib

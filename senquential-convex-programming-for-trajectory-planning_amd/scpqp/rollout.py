@@ -41,6 +41,9 @@ nothing of the schedule.
 ``reset(..., tracker_accel=)`` puts the filter that also estimates the acceleration in the
 tracker's place (include/scpqp_tracker_accel.h): it runs on one manoeuvre piece and predicts a
 horizon that brakes to a stop.
+``reset(..., governor=)`` commands the acceleration state of every (realisation, vehicle) from
+the step's own plan (include/scpqp_governor.h): brake on a predicted conflict, else return to
+the cruise speed.
 """
 from __future__ import annotations
 
@@ -210,6 +213,7 @@ class ClosedLoopBatch:
         self.imm_rows = None           # the bank (trk, sw) of reset(..., imm=)
         self.margin = None             # (kappa, m_max) of reset(..., margin=)
         self.obst_margin = None
+        self.gov_rows = None           # the governor tuning of reset(..., governor=)
         self.trace = trace     # keep every step's solve inputs and per-SCP-iteration trace
         self.out = self.solver.alloc_out(self.B, trace=trace)
         self.history = []
@@ -222,7 +226,7 @@ class ClosedLoopBatch:
     def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0, truth=None,
               obstacles=None, sensing=None, obstacle_sensing=None, sense_seed=None,
               estimator=None, tracker=None, manoeuvres=None, tracker_accel=None, imm=None,
-              margin=None):
+              margin=None, governor=None):
         """main.py:73-75: vehiclePathFullRes[:, v, 0] = x0; the control path holds
         scenario.u0 for the first ticks_delay_u + ticks_per_sim + 1 ticks.
 
@@ -309,7 +313,29 @@ class ClosedLoopBatch:
         ``tracker_accel=`` or ``imm=`` (the five-state ``tracker=`` has no acceleration row).
         The record gains ``obst_margin`` [B, nObst, Hp].  The realised-path metrics stay what
         they are: they measure the truth, not the inflated distance.  None: the rollout is
-        what it was; ``(0, m_max)`` gives the same rollout bitwise."""
+        what it was; ``(0, m_max)`` gives the same rollout bitwise.
+
+        ``governor`` [B, nVeh, 7] (scpqp/governor.py; include/scpqp_governor.h): after the solve
+        of step i the governor looks at that step's plan (``x0``, ``traj``, the ``obst`` and the
+        margins the solve was given, the required distances of each realisation's variant,
+        ``t_hold = dt``, ``t_back = delay_u``) and commands an acceleration, which becomes the
+        plant's ``x[4]`` at the start of step i + 1: the one-step compute delay the steering has,
+        and no transport delay of its own.  Column 4 of the delay compensation's input is the
+        acceleration in force at the step's first tick, after the sensor and the estimator: the
+        controller issued that command and knows it.  The record gains ``accel_cmd``,
+        ``gov_k_conf`` and ``gov_clear`` [B, nVeh].  The steering limit keeps reading the
+        realised speed (at speed 0 it is the mechanical limit).  Validated here, before
+        anything is launched; None, or a tuning in which every row is off: nothing is allocated
+        or launched and the rollout is what it was."""
+        if governor is not None:
+            from . import governor as GOV
+            gv = governor.detach().cpu().numpy() if isinstance(governor, torch.Tensor) \
+                else np.asarray(governor, float)
+            if tuple(gv.shape) != (self.B, self.nV, GOV.NP):
+                raise ValueError(f"governor must be [B, nVeh, 7] = [{self.B}, {self.nV}, 7]")
+            GOV.validate(gv)
+            if GOV.is_off(gv):
+                governor = None
         if margin is not None:
             from . import margin as MG
             if tracker_accel is None and imm is None:
@@ -486,6 +512,12 @@ class ClosedLoopBatch:
         self.man_rows = None if manoeuvres is None else torch.as_tensor(
             manoeuvres, dtype=torch.float64, device=self.device).contiguous().clone()
         self.obst_state = None         # this step's snapshot rows
+        self.gov_rows = self.gov_dreq = None
+        if governor is not None:
+            self.gov_rows = torch.as_tensor(governor, dtype=torch.float64,
+                                            device=self.device).contiguous().clone()
+            # the required centre distances of every realisation's variant
+            self.gov_dreq = GOV.required(self.sc, self.variants, self.variant_of, self.device)
         self.last_path = None
         self.u_prev = None
         self.history = []
@@ -635,7 +667,13 @@ class ClosedLoopBatch:
         horizon = sc.delay_x + sc.dt + sc.delay_u
         # with a seed: this step's noise stream (epoch i), else None and nothing changes
         rng = None if self.rng is None else self.rng.at(i)
-        x0, dtraj = PL.delay_compensate(self.params, x_in.contiguous(), u_hold, horizon,
+        x_plan = x_in
+        if self.gov_rows is not None:
+            # the acceleration in force at tick_now is the governor's own command: with a
+            # measurement delay the compensation assumes it over the whole span
+            x_plan = x_in.clone()
+            x_plan[:, :, 4] = self.state[:, :, 4]
+        x0, dtraj = PL.delay_compensate(self.params, x_plan.contiguous(), u_hold, horizon,
                                         noise=self.noise, h_max=self.h_max, device=self.device,
                                         rng=rng)
         # SCP solve, warm-started from the previous controller output (SCP_controller.py:42-43)
@@ -646,6 +684,12 @@ class ClosedLoopBatch:
         out = self.solver.solve(x0, u_hold, ec_noise, u_warm=u_warm, obst=obst, out=self.out,
                                 variant=self.variant_of, obst_margin=self.obst_margin)
         self.u_prev = out.u.clone()
+        gov = None
+        if self.gov_rows is not None:
+            # the speed governor (include/scpqp_governor.h) on this step's plan
+            from . import governor as GOV
+            gov = GOV.step(self.gov_rows, x0, out.traj, None if obst is None else obst.contiguous(),
+                           self.obst_margin, *self.gov_dreq, sc.dt, sc.delay_u, hp_max=Hp)
         if self.timing:
             torch.cuda.synchronize(self.device)
         t_ctrl = time.perf_counter() - t_step
@@ -670,6 +714,9 @@ class ClosedLoopBatch:
                                          manoeuvres=self.man_rows, check_off=False)
         self.last_path = path
         self.state = path[:, :, tps, :].contiguous()
+        if gov is not None:
+            # the command takes effect at the start of step i + 1
+            self.state[:, :, 4] = gov[0]
         rec = dict(x0=x0, u0=u_hold, umax=umax, U=U, traj=out.traj.clone(),
                    n_scp=out.n_scp.clone(), status=out.status.clone())
         if rng is not None:
@@ -687,6 +734,8 @@ class ClosedLoopBatch:
             rec["obst_est"], rec["obst_nis"], rec["obst_meas"], rec["obst_mu"] = self.trk_rec
         if self.obst_margin is not None:
             rec["obst_margin"] = self.obst_margin   # what the solve added to its safety distances
+        if gov is not None:
+            rec["accel_cmd"], rec["gov_k_conf"], rec["gov_clear"] = gov
         if self.sense_rows is not None:
             rec["x_meas"] = x_meas  # what the controller was told of the vehicles
             rec["delivered"] = delivered

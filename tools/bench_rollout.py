@@ -19,6 +19,7 @@ realisation per spawned single-threaded worker.
                                   | --track-imm [--imm-stay P]]
                                   [--obstacle-brake DECEL | --obstacle-weave DYAW]
                                   [--margin-kappa K [--margin-max M]]
+                                  [--govern [--gov-brake A] [--gov-look N] [--gov-band M]]
 
 Prints one JSON line: realisation-steps/s on the GPU and the CPU, and the
 largest state difference between the two on the CPU sample.  ``--noise-seed S``
@@ -89,6 +90,13 @@ obstacles.
 (default MARGIN_MAX); it needs ``--track-accel`` or ``--track-imm`` and adds ``mean_margin``,
 ``mean_margin_last_horizon_step`` and ``frac_margin_at_max``.  ``frac_steps_at_scp_cap`` (every
 run) is the share of solves that ran into the SCP iteration cap.
+``--govern`` runs the timed batch with the speed governor (include/scpqp_governor.h;
+``reset(..., governor=)``): ``governor.rows`` with V_REF each vehicle's initial speed,
+``--gov-brake A`` m/s^2 (default GOV_BRAKE), ``--gov-look N`` plan steps (default GOV_LOOK) and
+``--gov-band M`` metres (default GOV_BAND), A_ACC = GOV_ACC, K_V = GOV_KV and no slew limit.  It
+runs in every run of the tool, the comparison runs included, and adds ``gov_frac_braking`` (the
+share of vehicle-steps with a negative command) and ``gov_frac_conflict`` (with a predicted
+conflict).  ``mean_speed`` (every run) is the mean realised speed at the end of the MPC steps.
 """
 import json
 import multiprocessing as mp
@@ -106,6 +114,10 @@ SCENARIOS = ("circle4", "frog", "parallel5")
 WEAVE_SECONDS = 2.0      # each half of --obstacle-weave's lane change
 BRAKE_SECONDS = 1000.0   # --obstacle-brake's piece: longer than any obstacle needs to stand
 MARGIN_MAX = 2.0         # metres: --margin-max's default, a choice (half an obstacle's length)
+# --govern's defaults, choices made before any run: the deceleration the braking obstacles of
+# --obstacle-brake 3 use, half of the frog horizon, no extra clearance, a gentle return to cruise
+GOV_BRAKE, GOV_LOOK, GOV_BAND = 3.0, 5, 0.0
+GOV_ACC, GOV_KV = 1.0, 0.5
 
 
 def make_scenario(name):
@@ -274,6 +286,17 @@ def main():
         margin = (kappa, m_max)
     elif "--margin-max" in argv:
         raise SystemExit("--margin-max needs --margin-kappa")
+    govern = "--govern" in argv
+    if govern:
+        argv.remove("--govern")
+    gov_opt = {"brake": GOV_BRAKE, "look": GOV_LOOK, "band": GOV_BAND}
+    for key in gov_opt:
+        if f"--gov-{key}" in argv:
+            at = argv.index(f"--gov-{key}")
+            gov_opt[key] = float(argv[at + 1])
+            del argv[at:at + 2]
+            if not govern:
+                raise SystemExit(f"--gov-{key} needs --govern")
     for key in holds:
         if f"--{key}-hold" in argv:
             at = argv.index(f"--{key}-hold")
@@ -372,6 +395,14 @@ def main():
             md.fixed(1, "dur", WEAVE_SECONDS).fixed(1, "dyaw", man_opt["weave"])
             md.fixed(2, "dur", WEAVE_SECONDS).fixed(2, "dyaw", -man_opt["weave"])
         man_kw = dict(manoeuvres=md.sample(B, device="cuda"))
+    if govern:
+        from scpqp import governor as GOV
+        try:
+            man_kw["governor"] = GOV.rows(B, sc.nVeh, v_ref=x_init[:, :, 3], a_acc=GOV_ACC,
+                                          a_brake=gov_opt["brake"], k_v=GOV_KV,
+                                          look=gov_opt["look"], band=gov_opt["band"])
+        except ValueError as e:
+            raise SystemExit(f"--govern: {e}") from None
     cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw, **trk_kw,
              **man_kw)
     cl.run(1)                      # warm-up (library load, first launches)
@@ -380,7 +411,11 @@ def main():
              **man_kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    hist = cl.run(steps)
+    speeds = []
+    for _ in range(steps):
+        cl.step()
+        speeds.append(cl.state[:, :, 3].clone())
+    hist = cl.history
     torch.cuda.synchronize()
     gpu_s = time.perf_counter() - t0
     state = cl.state.cpu().numpy()
@@ -403,6 +438,16 @@ def main():
         "frac_steps_at_scp_cap": float(np.mean([(h["n_scp"] >= R.MAX_SCP_ITER).float().mean().item()
                                                 for h in hist])),
     }
+    out["mean_speed"] = float(torch.stack(speeds).mean().item())
+    if govern:
+        acc = torch.stack([h["accel_cmd"] for h in hist])           # [steps, B, nVeh]
+        kc = torch.stack([h["gov_k_conf"] for h in hist])
+        out["govern"] = dict(a_brake=gov_opt["brake"], look=gov_opt["look"], band=gov_opt["band"],
+                             a_acc=GOV_ACC, k_v=GOV_KV, v_ref="initial speed")
+        out["gov_frac_braking"] = float((acc < 0).float().mean().item())
+        out["gov_frac_conflict"] = float((kc >= 0).float().mean().item())
+        out["min_speed"] = float(torch.stack(speeds).min().item())
+        out["status_words"] = sorted(set(torch.stack([h["status"] for h in hist]).flatten().tolist()))
     if metrics:
         out["metrics"] = summary
     if n_var:

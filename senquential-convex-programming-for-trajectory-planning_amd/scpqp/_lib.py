@@ -2,8 +2,8 @@
 ``include/scpqp_metrics.h``, ``include/scpqp_variants.h``, ``include/scpqp_truth.h``,
 ``include/scpqp_obstacles.h``, ``include/scpqp_sensing.h``, ``include/scpqp_estimator.h``,
 ``include/scpqp_tracker.h``, ``include/scpqp_manoeuvres.h``,
-``include/scpqp_tracker_accel.h``, ``include/scpqp_imm.h``, ``include/scpqp_margin.h`` and
-``include/scpqp_governor.h`` (the C-ABI of the HIP library).
+``include/scpqp_tracker_accel.h``, ``include/scpqp_imm.h``, ``include/scpqp_margin.h``,
+``include/scpqp_governor.h`` and ``include/scpqp_yield.h`` (the C-ABI of the HIP library).
 
 The shared library ``libscpqp.so`` is built in-tree (``__graft_entry__.build()``
 or ``python -m scpqp.build``).  There is no CPU fallback: if the library or a
@@ -281,6 +281,14 @@ GOV_FIELDS = ("v_ref", "a_acc", "a_brake", "k_v", "j_max", "look", "band")
 # every symbol include/scpqp_governor.h declares (checked by tests/test_governor_host.py)
 GOV_EXPORTS = ("scpqp_governor_step",)
 
+YLD_NP = 10
+YLD_PRIO, YLD_A_EASE, YLD_S_STAND = 7, 8, 9
+YLD_PRIO_MAX = 1 << 20
+YLD_FIELDS = GOV_FIELDS + ("prio", "a_ease", "s_stand")
+
+# every symbol include/scpqp_yield.h declares (checked by tests/test_yield_host.py)
+YLD_EXPORTS = ("scpqp_yield_step",)
+
 _lib = None
 
 
@@ -447,6 +455,11 @@ def load(path=None):
         D, I = C.c_double, C.c_int32
         lib.scpqp_governor_step.argtypes = [I, I, I, I, D, D, V, V, V, V, V, V, V, V, V, V, V, V]
         lib.scpqp_governor_step.restype = C.c_int
+    # likewise an A/B build from before the right of way
+    if path is None or hasattr(lib, "scpqp_yield_step"):
+        D, I = C.c_double, C.c_int32
+        lib.scpqp_yield_step.argtypes = [I, I, I, I, D, D] + [V] * 15
+        lib.scpqp_yield_step.restype = C.c_int
     if path is None:
         _lib = lib
     return lib

@@ -44,6 +44,9 @@ horizon that brakes to a stop.
 ``reset(..., governor=)`` commands the acceleration state of every (realisation, vehicle) from
 the step's own plan (include/scpqp_governor.h): brake on a predicted conflict, else return to
 the cruise speed.
+``reset(..., right_of_way=)`` puts the governor with ranks and graded braking in its place
+(include/scpqp_yield.h): in a conflict between two vehicles only the outranked one yields, with
+a deceleration sized to stop before the conflict.
 """
 from __future__ import annotations
 
@@ -214,6 +217,7 @@ class ClosedLoopBatch:
         self.margin = None             # (kappa, m_max) of reset(..., margin=)
         self.obst_margin = None
         self.gov_rows = None           # the governor tuning of reset(..., governor=)
+        self.yld_rows = None           # the tuning of reset(..., right_of_way=)
         self.trace = trace     # keep every step's solve inputs and per-SCP-iteration trace
         self.out = self.solver.alloc_out(self.B, trace=trace)
         self.history = []
@@ -226,7 +230,7 @@ class ClosedLoopBatch:
     def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0, truth=None,
               obstacles=None, sensing=None, obstacle_sensing=None, sense_seed=None,
               estimator=None, tracker=None, manoeuvres=None, tracker_accel=None, imm=None,
-              margin=None, governor=None):
+              margin=None, governor=None, right_of_way=None):
         """main.py:73-75: vehiclePathFullRes[:, v, 0] = x0; the control path holds
         scenario.u0 for the first ticks_delay_u + ticks_per_sim + 1 ticks.
 
@@ -326,7 +330,28 @@ class ClosedLoopBatch:
         ``gov_k_conf`` and ``gov_clear`` [B, nVeh].  The steering limit keeps reading the
         realised speed (at speed 0 it is the mechanical limit).  Validated here, before
         anything is launched; None, or a tuning in which every row is off: nothing is allocated
-        or launched and the rollout is what it was."""
+        or launched and the rollout is what it was.
+
+        ``right_of_way`` [B, nVeh, 10] (scpqp/yielding.py; include/scpqp_yield.h) takes the
+        governor's place in the step: the same inputs, ``t_hold`` and ``t_back``, the same write
+        of ``state[:, :, 4]`` and the same column-4 rule for the delay compensation, with a rank
+        per vehicle and a deceleration sized to stop before the conflict.  Passing it together
+        with ``governor`` is refused.  The record gains ``accel_cmd``, ``gov_k_conf``,
+        ``gov_clear``, ``gov_k_any``, ``gov_who`` and ``gov_d_stop`` [B, nVeh].  Validated here,
+        before anything is launched; None, or every row off: nothing is allocated or launched
+        and the rollout is what it was."""
+        if right_of_way is not None:
+            from . import yielding as YLD
+            if governor is not None:
+                raise ValueError("right_of_way takes the governor's place: pass one of "
+                                 "governor= and right_of_way=")
+            yv = right_of_way.detach().cpu().numpy() if isinstance(right_of_way, torch.Tensor) \
+                else np.asarray(right_of_way, float)
+            if tuple(yv.shape) != (self.B, self.nV, YLD.NP):
+                raise ValueError(f"right_of_way must be [B, nVeh, 10] = [{self.B}, {self.nV}, 10]")
+            YLD.validate(yv)
+            if YLD.is_off(yv):
+                right_of_way = None
         if governor is not None:
             from . import governor as GOV
             gv = governor.detach().cpu().numpy() if isinstance(governor, torch.Tensor) \
@@ -518,6 +543,11 @@ class ClosedLoopBatch:
                                             device=self.device).contiguous().clone()
             # the required centre distances of every realisation's variant
             self.gov_dreq = GOV.required(self.sc, self.variants, self.variant_of, self.device)
+        self.yld_rows = None
+        if right_of_way is not None:
+            self.yld_rows = torch.as_tensor(right_of_way, dtype=torch.float64,
+                                            device=self.device).contiguous().clone()
+            self.gov_dreq = YLD.required(self.sc, self.variants, self.variant_of, self.device)
         self.last_path = None
         self.u_prev = None
         self.history = []
@@ -668,7 +698,7 @@ class ClosedLoopBatch:
         # with a seed: this step's noise stream (epoch i), else None and nothing changes
         rng = None if self.rng is None else self.rng.at(i)
         x_plan = x_in
-        if self.gov_rows is not None:
+        if self.gov_rows is not None or self.yld_rows is not None:
             # the acceleration in force at tick_now is the governor's own command: with a
             # measurement delay the compensation assumes it over the whole span
             x_plan = x_in.clone()
@@ -689,6 +719,11 @@ class ClosedLoopBatch:
             # the speed governor (include/scpqp_governor.h) on this step's plan
             from . import governor as GOV
             gov = GOV.step(self.gov_rows, x0, out.traj, None if obst is None else obst.contiguous(),
+                           self.obst_margin, *self.gov_dreq, sc.dt, sc.delay_u, hp_max=Hp)
+        elif self.yld_rows is not None:
+            # the same with right of way and graded braking (include/scpqp_yield.h)
+            from . import yielding as YLD
+            gov = YLD.step(self.yld_rows, x0, out.traj, None if obst is None else obst.contiguous(),
                            self.obst_margin, *self.gov_dreq, sc.dt, sc.delay_u, hp_max=Hp)
         if self.timing:
             torch.cuda.synchronize(self.device)
@@ -735,7 +770,9 @@ class ClosedLoopBatch:
         if self.obst_margin is not None:
             rec["obst_margin"] = self.obst_margin   # what the solve added to its safety distances
         if gov is not None:
-            rec["accel_cmd"], rec["gov_k_conf"], rec["gov_clear"] = gov
+            rec["accel_cmd"], rec["gov_k_conf"], rec["gov_clear"] = gov[:3]
+            if len(gov) > 3:
+                rec["gov_k_any"], rec["gov_who"], rec["gov_d_stop"] = gov[3:]
         if self.sense_rows is not None:
             rec["x_meas"] = x_meas  # what the controller was told of the vehicles
             rec["delivered"] = delivered

@@ -19,7 +19,9 @@ realisation per spawned single-threaded worker.
                                   | --track-imm [--imm-stay P]]
                                   [--obstacle-brake DECEL | --obstacle-weave DYAW]
                                   [--margin-kappa K [--margin-max M]]
-                                  [--govern [--gov-brake A] [--gov-look N] [--gov-band M]]
+                                  [--govern [--gov-brake A] [--gov-look N] [--gov-band M]
+                                   [--gov-prio index|reverse|equal] [--gov-ease A]
+                                   [--gov-stand S]]
 
 Prints one JSON line: realisation-steps/s on the GPU and the CPU, and the
 largest state difference between the two on the CPU sample.  ``--noise-seed S``
@@ -97,6 +99,14 @@ run) is the share of solves that ran into the SCP iteration cap.
 runs in every run of the tool, the comparison runs included, and adds ``gov_frac_braking`` (the
 share of vehicle-steps with a negative command) and ``gov_frac_conflict`` (with a predicted
 conflict).  ``mean_speed`` (every run) is the mean realised speed at the end of the MPC steps.
+``--gov-prio index|reverse|equal``, ``--gov-ease A`` and ``--gov-stand S`` (each needs
+``--govern``) put the governor with right of way and graded braking in its place
+(include/scpqp_yield.h; ``reset(..., right_of_way=)``): the rank of vehicle v is v, n_veh - 1 - v
+or the same for all (default ``equal``), the gentlest deceleration A m/s^2 (default: the
+``--gov-brake`` value, full braking) and the standing speed S m/s (default YLD_STAND: the rule
+off).  With any of the three the line adds ``gov_frac_any_conflict`` (a conflict with anybody,
+counted or not), ``gov_frac_yield_to_vehicle`` and ``gov_mean_d_stop``; without them the line is
+what it was.
 """
 import json
 import multiprocessing as mp
@@ -118,6 +128,9 @@ MARGIN_MAX = 2.0         # metres: --margin-max's default, a choice (half an obs
 # --obstacle-brake 3 use, half of the frog horizon, no extra clearance, a gentle return to cruise
 GOV_BRAKE, GOV_LOOK, GOV_BAND = 3.0, 5, 0.0
 GOV_ACC, GOV_KV = 1.0, 0.5
+# the right-of-way defaults, chosen before any run as well: equal ranks, A_EASE = A_BRAKE and no
+# standing rule, which is the governor itself
+YLD_PRIO, YLD_STAND = "equal", 0.0
 
 
 def make_scenario(name):
@@ -297,6 +310,16 @@ def main():
             del argv[at:at + 2]
             if not govern:
                 raise SystemExit(f"--gov-{key} needs --govern")
+    yld_opt = {}
+    for key, conv in (("prio", str), ("ease", float), ("stand", float)):
+        if f"--gov-{key}" in argv:
+            at = argv.index(f"--gov-{key}")
+            yld_opt[key] = conv(argv[at + 1])
+            del argv[at:at + 2]
+            if not govern:
+                raise SystemExit(f"--gov-{key} needs --govern")
+    if yld_opt.get("prio", YLD_PRIO) not in ("index", "reverse", "equal"):
+        raise SystemExit("--gov-prio takes index, reverse or equal")
     for key in holds:
         if f"--{key}-hold" in argv:
             at = argv.index(f"--{key}-hold")
@@ -401,6 +424,14 @@ def main():
             man_kw["governor"] = GOV.rows(B, sc.nVeh, v_ref=x_init[:, :, 3], a_acc=GOV_ACC,
                                           a_brake=gov_opt["brake"], k_v=GOV_KV,
                                           look=gov_opt["look"], band=gov_opt["band"])
+            if yld_opt:
+                from scpqp import yielding as YLD
+                v = np.arange(sc.nVeh)
+                prio = {"index": v, "reverse": sc.nVeh - 1 - v, "equal": 0 * v}[
+                    yld_opt.get("prio", YLD_PRIO)]
+                man_kw["right_of_way"] = YLD.from_governor(
+                    man_kw.pop("governor"), prio, a_ease=yld_opt.get("ease"),
+                    s_stand=yld_opt.get("stand", YLD_STAND))
         except ValueError as e:
             raise SystemExit(f"--govern: {e}") from None
     cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw, **trk_kw,
@@ -446,6 +477,17 @@ def main():
                              a_acc=GOV_ACC, k_v=GOV_KV, v_ref="initial speed")
         out["gov_frac_braking"] = float((acc < 0).float().mean().item())
         out["gov_frac_conflict"] = float((kc >= 0).float().mean().item())
+        if yld_opt:
+            out["govern"].update(prio=yld_opt.get("prio", YLD_PRIO),
+                                 a_ease=yld_opt.get("ease", gov_opt["brake"]),
+                                 s_stand=yld_opt.get("stand", YLD_STAND))
+            ka = torch.stack([h["gov_k_any"] for h in hist])
+            who = torch.stack([h["gov_who"] for h in hist])
+            ds = torch.stack([h["gov_d_stop"] for h in hist])
+            out["gov_frac_any_conflict"] = float((ka >= 0).float().mean().item())
+            out["gov_frac_yield_to_vehicle"] = float((who >= sc.nObst).float().mean().item())
+            fin = ds[torch.isfinite(ds)]
+            out["gov_mean_d_stop"] = float(fin.mean().item()) if fin.numel() else None
         out["min_speed"] = float(torch.stack(speeds).min().item())
         out["status_words"] = sorted(set(torch.stack([h["status"] for h in hist]).flatten().tolist()))
     if metrics:

@@ -19,6 +19,7 @@
 #include <stdio.h>
 
 #include "scpqp_bicycle.h"
+#include "scpqp_ekf.h"
 #include "scpqp_estimator.h"
 
 int scpqp_fail_(int code, const char* msg);   // scpqp.hip: sets scpqp_last_error()
@@ -26,6 +27,7 @@ int scpqp_fail_(int code, const char* msg);   // scpqp.hip: sets scpqp_last_erro
 namespace {
 
 using namespace scpqp_plant_dev;   // NX, Veh, flow, steps_for
+using scpqp_ekf_dev::correct;      // with every state measured: H = I
 
 constexpr int NS = SCPQP_EST_NS;
 constexpr int NP = SCPQP_EST_NP;
@@ -92,85 +94,6 @@ __device__ __forceinline__ void propagate(double (&P)[NS][NS], const Trans& f,
 #pragma unroll
         for (int c = 0; c < r; ++c) P[r][c] = P[c][r];
     }
-}
-
-// the measurement update with H = I on a symmetric P; false on a bad pivot
-__device__ __forceinline__ bool correct(double (&xs)[NS], double (&P)[NS][NS],
-                                        const double (&ms)[NS], const double (&r2)[NS],
-                                        double& nis) {
-    double Lc[NS][NS], inv[NS];
-    bool ok = true;
-    // S = P + R = L L'
-#pragma unroll
-    for (int j = 0; j < NS; ++j) {
-        double d = P[j][j] + r2[j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) d -= Lc[j][k] * Lc[j][k];
-        ok &= d > 0.0 && isfinite(d);
-        Lc[j][j] = sqrt(d);
-        inv[j] = 1.0 / Lc[j][j];
-#pragma unroll
-        for (int i = j + 1; i < NS; ++i) {
-            double s = P[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) s -= Lc[i][k] * Lc[j][k];
-            Lc[i][j] = s * inv[j];
-        }
-    }
-    if (!ok) return false;
-    // z = L^-1 y, nis = z' z, w = L'^-1 z = S^-1 y
-    double z[NS], w[NS];
-    nis = 0.0;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        double s = ms[i] - xs[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) s -= Lc[i][k] * z[k];
-        z[i] = s * inv[i];
-        nis += z[i] * z[i];
-    }
-#pragma unroll
-    for (int i = NS - 1; i >= 0; --i) {
-        double s = z[i];
-#pragma unroll
-        for (int k = i + 1; k < NS; ++k) s -= Lc[k][i] * w[k];
-        w[i] = s * inv[i];
-    }
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        double s = xs[i];
-#pragma unroll
-        for (int k = 0; k < NS; ++k) s += P[i][k] * w[k];
-        xs[i] = s;
-    }
-    // W = L^-1 P, P <- P - W' W = P - P S^-1 P
-    double W[NS][NS];
-#pragma unroll
-    for (int c = 0; c < NS; ++c) {
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-            double s = P[i][c];
-#pragma unroll
-            for (int k = 0; k < i; ++k) s -= Lc[i][k] * W[k][c];
-            W[i][c] = s * inv[i];
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < NS; ++r) {
-#pragma unroll
-        for (int c = r; c < NS; ++c) {
-            double s = P[r][c];
-#pragma unroll
-            for (int k = 0; k < NS; ++k) s -= W[k][r] * W[k][c];
-            P[r][c] = s;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < NS; ++r) {
-#pragma unroll
-        for (int c = 0; c < r; ++c) P[r][c] = P[c][r];
-    }
-    return true;
 }
 
 // one lane per (b, v)

@@ -22,9 +22,8 @@
 #include <limits.h>
 #include <math.h>
 
+#include "scpqp_entry_checks.h"
 #include "scpqp_governor.h"
-
-int scpqp_fail_(int code, const char* msg);   // scpqp.hip: sets scpqp_last_error()
 
 namespace {
 
@@ -133,28 +132,11 @@ int scpqp_governor_step(int32_t n_veh, int32_t n_obst, int32_t hp_max, int32_t B
                         const double* obst_margin, const int32_t* hp, const double* dreq_obs,
                         const double* dreq_veh, const double* gov, double* a_cmd,
                         int32_t* k_conf, double* clear, void* stream) {
-    if (B < 0) return scpqp_fail_(SCPQP_E_ARG, "batch size < 0");
-    if (n_veh < 1 || n_veh > SCPQP_MAX_VEH) return scpqp_fail_(SCPQP_E_ARG, "n_veh out of range");
-    if (n_obst < 0 || n_obst > SCPQP_MAX_OBST) return scpqp_fail_(SCPQP_E_ARG, "n_obst out of range");
-    if (hp_max < 1 || hp_max > SCPQP_MAX_HP) return scpqp_fail_(SCPQP_E_ARG, "hp_max out of range");
-    if (!isfinite(t_hold) || !(t_hold > 0.0))
-        return scpqp_fail_(SCPQP_E_ARG, "t_hold must be finite and > 0");
-    if (!isfinite(t_back) || !(t_back >= 0.0))
-        return scpqp_fail_(SCPQP_E_ARG, "t_back must be finite and >= 0");
+    if (int rc = scpqp_host::conflict_step_checks(n_veh, n_obst, hp_max, B, t_hold, t_back, x0, traj,
+                                                  obst, dreq_obs, dreq_veh, gov, NP,
+                                                  "null gov rows array", a_cmd))
+        return rc < 0 ? rc : 0;
     const long long n = (long long)B * n_veh;
-    if (2 * n * hp_max > 0x7fffffffLL) return scpqp_fail_(SCPQP_E_SIZE, "B * n_veh * 2 * hp_max too large");
-    if (2LL * B * n_obst * hp_max > 0x7fffffffLL)
-        return scpqp_fail_(SCPQP_E_SIZE, "B * n_obst * 2 * hp_max too large");
-    const int widest = n_veh > n_obst ? (n_veh > NP ? n_veh : NP) : (n_obst > NP ? n_obst : NP);
-    if (n * widest > 0x7fffffffLL) return scpqp_fail_(SCPQP_E_SIZE, "B * n_veh * row width too large");
-    if (B == 0) return 0;
-    if (!x0) return scpqp_fail_(SCPQP_E_ARG, "null x0 array");
-    if (!traj) return scpqp_fail_(SCPQP_E_ARG, "null traj array");
-    if (!obst && n_obst > 0) return scpqp_fail_(SCPQP_E_ARG, "null obst array with n_obst > 0");
-    if (!dreq_obs && n_obst > 0) return scpqp_fail_(SCPQP_E_ARG, "null dreq_obs array with n_obst > 0");
-    if (!dreq_veh) return scpqp_fail_(SCPQP_E_ARG, "null dreq_veh array");
-    if (!gov) return scpqp_fail_(SCPQP_E_ARG, "null gov rows array");
-    if (!a_cmd) return scpqp_fail_(SCPQP_E_ARG, "null a_cmd array");
     constexpr int per = PT / GW;
     // with no obstacle the obstacle arrays are not the kernel's to look at
     hipLaunchKernelGGL(governor_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(PT), 0,

@@ -20,6 +20,7 @@
 #include "scpqp_manoeuvre_pose.h"
 #include "scpqp_manoeuvres.h"
 #include "scpqp_philox.h"
+#include "scpqp_rounding.h"
 
 int scpqp_fail_(int code, const char* msg);   // scpqp.hip: sets scpqp_last_error()
 
@@ -33,13 +34,8 @@ constexpr int PT = 256;   // threads per workgroup
 
 using scpqp_man_dev::State;
 
-// a * b + c in two roundings (include/scpqp_manoeuvres.h: __dadd_rn(mean, __dmul_rn(spread, xi))),
-// spelled with the operators under contract(off) as in obstacles.hip
-__device__ __forceinline__ double mul_add_2r(double a, double b, double c) {
-#pragma clang fp contract(off)
-    const double ab = a * b;
-    return ab + c;
-}
+// include/scpqp_manoeuvres.h: __dadd_rn(mean, __dmul_rn(spread, xi))
+using scpqp_round_dev::mul_add_2r;
 
 // the lane's class: 0 a schedule to walk, 1 off, 2 bad (include/scpqp_manoeuvres.h)
 __device__ __forceinline__ int lane_class(const double* __restrict__ r, const double* __restrict__ m) {

@@ -19,8 +19,8 @@
 // lanes compute and discard, the loop over the horizon has the same trip count in every thread,
 // and every exchange is a statement of its own, outside any && or ||.
 //
-// The horizon restates step 4 of include/scpqp_tracker_accel.h on `advance` of
-// scpqp_manoeuvre_pose.h, as imm.hip does (which is not edited).
+// The horizon is step 4 of include/scpqp_tracker_accel.h on `advance` of
+// scpqp_manoeuvre_pose.h, in the text of tracker_accel.hip and imm.hip.
 #include <hip/hip_runtime.h>
 
 #include <math.h>

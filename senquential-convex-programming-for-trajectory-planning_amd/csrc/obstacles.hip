@@ -19,6 +19,7 @@
 #include "scpqp_obstacle_pose.h"
 #include "scpqp_obstacles.h"
 #include "scpqp_philox.h"
+#include "scpqp_rounding.h"
 
 int scpqp_fail_(int code, const char* msg);   // scpqp.hip: sets scpqp_last_error()
 
@@ -29,13 +30,8 @@ constexpr int PT = 256;   // threads per workgroup
 
 using scpqp_obst_dev::Pose;
 
-// a * b + c in two roundings (include/scpqp_obstacles.h: __dadd_rn(mean, __dmul_rn(spread, xi))),
-// spelled with the operators under contract(off) as in plant.hip
-__device__ __forceinline__ double mul_add_2r(double a, double b, double c) {
-#pragma clang fp contract(off)
-    const double ab = a * b;
-    return ab + c;
-}
+// include/scpqp_obstacles.h: __dadd_rn(mean, __dmul_rn(spread, xi))
+using scpqp_round_dev::mul_add_2r;
 
 // one lane per (b, o, k): obst[b][o][0 / 1][k]
 __global__ __launch_bounds__(PT) void predict_kernel(int n, int hp, const double* __restrict__ rows,

@@ -33,6 +33,7 @@
 #include "scpqp_bicycle.h"
 #include "scpqp_noise.h"
 #include "scpqp_philox.h"
+#include "scpqp_rounding.h"
 #include "scpqp_truth.h"
 
 int scpqp_fail_(int code, const char* msg);   // scpqp.hip: sets scpqp_last_error()
@@ -43,14 +44,7 @@ using namespace scpqp_plant_dev;   // scpqp_bicycle.h: NX, Veh, VehT, bicycle, r
 
 constexpr int PT = 256;   // threads per workgroup
 
-// a * b + c in two roundings, the __dadd_rn(__dmul_rn(a, b), c) of include/scpqp_truth.h.
-// Spelled with the operators under contract(off): the two intrinsics are plain * and +
-// to the compiler, which would fuse them into one fma (one rounding) once inlined.
-__device__ __forceinline__ double mul_add_2r(double a, double b, double c) {
-#pragma clang fp contract(off)
-    const double ab = a * b;
-    return ab + c;
-}
+using scpqp_round_dev::mul_add_2r;   // the __dadd_rn(__dmul_rn(a, b), c) of include/scpqp_truth.h
 
 // one lane per (problem, vehicle): linspace(0, horizon, n_out) outputs.  kNoisy:
 // site 0 stream of (b_offset + b, v), counting on across the n_out - 1 spans.

@@ -17,11 +17,12 @@
 #include <math.h>
 #include <stdio.h>
 
+#include "scpqp_entry_checks.h"
 #include "scpqp_obstacle_pose.h"
 #include "scpqp_philox.h"
+#include "scpqp_rounding.h"
+#include "scpqp_sense_draw.h"
 #include "scpqp_sensing.h"
-
-int scpqp_fail_(int code, const char* msg);   // scpqp.hip: sets scpqp_last_error()
 
 namespace {
 
@@ -31,40 +32,11 @@ constexpr int PT = 256;   // threads per workgroup
 
 using scpqp_obst_dev::Pose;
 
-// a * b + c in two roundings (include/scpqp_sensing.h: every product and every sum is its
-// own rounding), spelled with the operators under contract(off) as in obstacles.hip
-__device__ __forceinline__ double mul_add_2r(double a, double b, double c) {
-#pragma clang fp contract(off)
-    const double ab = a * b;
-    return ab + c;
-}
-
-__device__ __forceinline__ double add_1r(double a, double b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-
-__device__ __forceinline__ double mul_1r(double a, double b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-
-struct Draw {
-    double z0, z1, u2;   // the normal pair and the [0, 1) uniform of one Philox call
-};
-
-// the call of counter (c0, epoch, c2, b_global), mapped as scpqp_noise.h maps it
-__device__ __forceinline__ Draw draw_at(const scpqp_sense_stream& st, uint32_t c0, uint32_t c2,
-                                        uint32_t b_global) {
-    uint32_t c[4] = {c0, st.epoch, c2, b_global};
-    scpqp_noise_dev::philox4x32_10(c, (uint32_t)st.seed, (uint32_t)(st.seed >> 32));
-    double u1, u2;
-    scpqp_noise_dev::uniforms(c, u1, u2);
-    const double r = sqrt(-2.0 * log(u1));
-    double sn, cs;
-    sincos(6.283185307179586 * u2, &sn, &cs);
-    return Draw{mul_1r(r, cs), mul_1r(r, sn), u2};
-}
+using scpqp_round_dev::add_1r;
+using scpqp_round_dev::mul_1r;
+using scpqp_round_dev::mul_add_2r;
+using scpqp_sense_dev::Draw;
+using scpqp_sense_dev::draw_at;
 
 // any field non-finite, a sigma < 0, P_DROP outside [0, 1], LAG < 0 or not whole
 __device__ __forceinline__ bool bad_sense_row(const double (&r)[NP]) {
@@ -275,11 +247,6 @@ int check_dist(const scpqp_sense_dist* d) {
     return 0;
 }
 
-int check_stream(const scpqp_sense_stream* st) {
-    if (!st) return scpqp_fail_(SCPQP_E_ARG, "null sensing stream");
-    return 0;
-}
-
 int launched() {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return scpqp_fail_(SCPQP_E_HIP, hipGetErrorString(e));
@@ -304,7 +271,7 @@ int scpqp_sense_measure(int32_t B, int32_t n_veh, int32_t n_ticks, int32_t k_mea
     if (B == 0) return 0;
     if (!x_path) return scpqp_fail_(SCPQP_E_ARG, "null x_path array");
     if (!sense) return scpqp_fail_(SCPQP_E_ARG, "null sense rows array");
-    if (int rc = check_stream(st)) return rc;
+    if (int rc = scpqp_host::check_stream(st)) return rc;
     if (!x_held) return scpqp_fail_(SCPQP_E_ARG, "null x_held array");
     if (!x_meas_out) return scpqp_fail_(SCPQP_E_ARG, "null output array");
     hipLaunchKernelGGL(measure_kernel, dim3((unsigned)((n + PT - 1) / PT)), dim3(PT), 0,
@@ -350,7 +317,7 @@ int scpqp_obstacles_predict_sensed(int32_t B, int32_t n_obst, int32_t hp, const 
     if (B == 0) return 0;
     if (!rows) return scpqp_fail_(SCPQP_E_ARG, "null rows array");
     if (!osense) return scpqp_fail_(SCPQP_E_ARG, "null osense rows array");
-    if (int rc = check_stream(st)) return rc;
+    if (int rc = scpqp_host::check_stream(st)) return rc;
     if (!obst_out) return scpqp_fail_(SCPQP_E_ARG, "null output array");
     // every block as the exact sensor predicts it; then, in stream order, the lanes whose
     // osense row is not all zero overwrite theirs.  An all-zero row so takes the code path of

@@ -7,6 +7,7 @@ The library is linked from separate translation units compiled in parallel:
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -51,25 +52,9 @@ def build_library(force=False, verbose=False, defines=(), out=None, csrc=None):
     src_dir = csrc or CSRC
     srcs = [os.path.join(src_dir, os.path.basename(x)) for x in SRCS]
     ksrc = os.path.join(src_dir, os.path.basename(KERNEL_SRC))
-    hdr = os.path.join(src_dir, os.path.basename(HEADER))
-    deps = srcs + [ksrc, hdr, os.path.join(src_dir, "scpqp_philox.h"),
-                   os.path.join(src_dir, "scpqp_obstacle_pose.h"),
-                   os.path.join(src_dir, "scpqp_manoeuvre_pose.h"),
-                   os.path.join(src_dir, "scpqp_bicycle.h"),
-                   os.path.join(INCLUDE, "scpqp_manoeuvres.h"),
-                   os.path.join(INCLUDE, "scpqp_obstacles.h"),
-                   os.path.join(INCLUDE, "scpqp_sensing.h"),
-                   os.path.join(INCLUDE, "scpqp_estimator.h"),
-                   os.path.join(INCLUDE, "scpqp_tracker.h"),
-                   os.path.join(INCLUDE, "scpqp_tracker_accel.h"),
-                   os.path.join(INCLUDE, "scpqp_imm.h"),
-                   os.path.join(INCLUDE, "scpqp_margin.h"),
-                   os.path.join(INCLUDE, "scpqp_governor.h"),
-                   os.path.join(INCLUDE, "scpqp_yield.h"),
-                   os.path.join(INCLUDE, "scpqp.h"), os.path.join(INCLUDE, "scpqp_noise.h"),
-                   os.path.join(INCLUDE, "scpqp_metrics.h"),
-                   os.path.join(INCLUDE, "scpqp_variants.h"),
-                   os.path.join(INCLUDE, "scpqp_truth.h"), __file__]
+    # every source and header a unit can include, so a new header is never missed
+    deps = (glob.glob(os.path.join(src_dir, "*.hip")) + glob.glob(os.path.join(src_dir, "*.h")) +
+            glob.glob(os.path.join(INCLUDE, "*.h")) + [__file__])
     if not force and os.path.exists(out):
         t = os.path.getmtime(out)
         if all(os.path.getmtime(d) <= t for d in deps):

@@ -1,13 +1,15 @@
 """Per-kernel ISA comparison of one HIP source between a git revision and the working tree.
 
-    python tools/kernel_isa_diff.py REV csrc/plant.hip kernel [kernel ...]
+    python tools/kernel_isa_diff.py REV csrc/plant.hip [kernel ...]
 
 Compiles the file at REV (with REV's headers) and in the working tree with the library's
 flags and ``-S --cuda-device-only``, cuts each named kernel's body out of the two listings
 (from its label to its function end), drops comments and blank lines, renumbers the local
 labels in order of appearance (new kernels in the file shift the compiler's numbering) and
 prints ``diff`` of the two: empty when the kernel is the same instruction for instruction.
-Exit status 1 if any kernel differs or is missing.
+With no kernel named, every kernel of either listing is compared (their
+``.amdhsa_kernel NAME`` directives list them, by mangled name).  Exit status 1 if any kernel
+differs or is missing on either side.
 """
 import difflib
 import os
@@ -31,9 +33,18 @@ def listing(tree, rel, out):
     return open(out).read().splitlines()
 
 
+def kernels_of(lines):
+    """The mangled names of the listing's kernels, in order."""
+    return [ln.split()[1] for ln in lines if ln.strip().startswith(".amdhsa_kernel ")]
+
+
 def body(lines, kernel):
-    """The instruction lines of the kernel whose mangled name holds <len><kernel>E."""
-    tag = re.compile(r"^(_Z\w*?%d%sE\w*):" % (len(kernel), re.escape(kernel)))
+    """The instruction lines of the kernel whose mangled name is `kernel` or holds
+    <len><kernel>E."""
+    if kernel.startswith("_Z"):
+        tag = re.compile(r"^(%s):" % re.escape(kernel))
+    else:
+        tag = re.compile(r"^(_Z\w*?%d%sE\w*):" % (len(kernel), re.escape(kernel)))
     out, on = [], False
     for ln in lines:
         if not on and tag.match(ln):
@@ -60,6 +71,8 @@ def main():
         subprocess.run(["tar", "-x", "-C", old], input=tar, check=True)
         a = listing(old, rel, os.path.join(tmp, "old.s"))
         b = listing(ROOT, rel, os.path.join(tmp, "new.s"))
+    if not kernels:
+        kernels = list(dict.fromkeys(kernels_of(a) + kernels_of(b)))
     for k in kernels:
         x, y = body(a, k), body(b, k)
         print(f"$ diff <(kernel_body {rev}:{rel} {k}) <(kernel_body worktree:{rel} {k})")

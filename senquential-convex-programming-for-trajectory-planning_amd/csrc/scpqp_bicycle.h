@@ -1,6 +1,7 @@
 // scpqp_bicycle.h — the bicycle right-hand side and its fixed-step RK4 flow (device
 // side of the plant: Model.py:61-87), shared by plant.hip (delay compensation, plant
-// step) and estimator.hip (the filter's prediction): one integrator, stated once.
+// step), estimator.hip (the filter's prediction) and drive.hip (the plant step behind a
+// longitudinal actuator): one integrator, stated once.
 #ifndef SCPQP_BICYCLE_H
 #define SCPQP_BICYCLE_H
 
@@ -57,6 +58,27 @@ __device__ __forceinline__ void bicycle(const double (&x)[NX], const VehT& p, do
     dx[5] = (p.uref - x[5]) / p.tau;
 }
 
+// a vehicle of the drive truth (include/scpqp_drive.h) with a lag or the hold rule: the
+// acceleration x[4] answers a_eff with the lag tau_a (lag == false: it is constant), and with
+// hold the brakes do not push a standing vehicle backwards.  A lane with neither is a VehT.
+struct VehD : VehT {
+    double a_eff, tau_a;
+    bool lag, hold;
+};
+
+__device__ __forceinline__ void bicycle(const double (&x)[NX], const VehD& p, double (&dx)[NX]) {
+    const double L = p.lf + p.lr, R = p.lr / L;
+    const double tu = tan(x[5]);
+    const double vc = x[3] * sqrt(1.0 + (R * tu) * (R * tu));
+    const double beta = atan(R * tu);
+    dx[0] = vc * cos(x[2] + beta) + p.n0;
+    dx[1] = vc * sin(x[2] + beta) + p.n1;
+    dx[2] = vc * tu * cos(beta) / L;
+    dx[3] = (p.hold && !(x[3] > 0.0) && x[4] < 0.0) ? 0.0 : x[4];
+    dx[4] = p.lag ? (p.a_eff - x[4]) / p.tau_a : 0.0;
+    dx[5] = (p.uref - x[5]) / p.tau;
+}
+
 using scpqp_noise_dev::Stream;
 
 // kNoisy: p.n0, p.n1 are redrawn before each of the four evaluations (c0 order
@@ -87,6 +109,18 @@ template <bool kNoisy, class VehX>
 __device__ __forceinline__ void flow(double (&x)[NX], VehX& p, double T, int n, Stream& ns) {
     const double h = T / n;
     for (int s = 0; s < n; ++s) rk4<kNoisy>(x, p, h, ns);
+}
+
+// flow() of a VehD: with hold, a speed that was >= 0 before an RK4 step and is < 0 after it
+// is set to exactly 0 (include/scpqp_drive.h)
+template <bool kNoisy>
+__device__ __forceinline__ void flow_drive(double (&x)[NX], VehD& p, double T, int n, Stream& ns) {
+    const double h = T / n;
+    for (int s = 0; s < n; ++s) {
+        const double s0 = x[3];
+        rk4<kNoisy>(x, p, h, ns);
+        if (p.hold && s0 >= 0.0 && x[3] < 0.0) x[3] = 0.0;
+    }
 }
 
 __device__ __forceinline__ int steps_for(double T, double hmax) {

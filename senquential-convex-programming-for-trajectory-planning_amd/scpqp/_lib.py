@@ -3,7 +3,8 @@
 ``include/scpqp_obstacles.h``, ``include/scpqp_sensing.h``, ``include/scpqp_estimator.h``,
 ``include/scpqp_tracker.h``, ``include/scpqp_manoeuvres.h``,
 ``include/scpqp_tracker_accel.h``, ``include/scpqp_imm.h``, ``include/scpqp_margin.h``,
-``include/scpqp_governor.h`` and ``include/scpqp_yield.h`` (the C-ABI of the HIP library).
+``include/scpqp_governor.h``, ``include/scpqp_yield.h`` and ``include/scpqp_drive.h`` (the C-ABI
+of the HIP library).
 
 The shared library ``libscpqp.so`` is built in-tree (``__graft_entry__.build()``
 or ``python -m scpqp.build``).  There is no CPU fallback: if the library or a
@@ -289,6 +290,22 @@ YLD_FIELDS = GOV_FIELDS + ("prio", "a_ease", "s_stand")
 # every symbol include/scpqp_yield.h declares (checked by tests/test_yield_host.py)
 YLD_EXPORTS = ("scpqp_yield_step",)
 
+DRIVE_NP = 6
+(DRIVE_TAU_A, DRIVE_GAIN_A, DRIVE_BIAS_A, DRIVE_A_MAX, DRIVE_B_MAX, DRIVE_HOLD) = range(DRIVE_NP)
+DRIVE_FIELDS = ("tau_a", "gain_a", "bias_a", "a_max", "b_max", "hold")
+NOISE_SITE_DRIVE = 9
+
+
+class DriveDist(C.Structure):
+    """scpqp_drive_dist (include/scpqp_drive.h)."""
+    _fields_ = [("n_veh", C.c_int32), ("pad0", C.c_int32),
+                ("mean", (C.c_double * MAX_VEH) * DRIVE_NP), ("field", TruthField * DRIVE_NP),
+                ("seed", C.c_uint64), ("b_offset", C.c_uint32), ("pad1", C.c_uint32)]
+
+
+# every symbol include/scpqp_drive.h declares (checked by tests/test_drive_host.py)
+DRIVE_EXPORTS = ("scpqp_plant_step_drive", "scpqp_drive_fill_ideal", "scpqp_drive_sample")
+
 _lib = None
 
 
@@ -460,6 +477,15 @@ def load(path=None):
         D, I = C.c_double, C.c_int32
         lib.scpqp_yield_step.argtypes = [I, I, I, I, D, D] + [V] * 15
         lib.scpqp_yield_step.restype = C.c_int
+    # likewise an A/B build from before the drive truth
+    if path is None or hasattr(lib, "scpqp_plant_step_drive"):
+        D, I = C.c_double, C.c_int32
+        lib.scpqp_plant_step_drive.argtypes = [PP, I, I, D, V, V, V, V, NP, V, V, V, D, V]
+        lib.scpqp_plant_step_drive.restype = C.c_int
+        lib.scpqp_drive_fill_ideal.argtypes = [I, I, V, V]
+        lib.scpqp_drive_fill_ideal.restype = C.c_int
+        lib.scpqp_drive_sample.argtypes = [C.POINTER(DriveDist), I, V, V]
+        lib.scpqp_drive_sample.restype = C.c_int
     if path is None:
         _lib = lib
     return lib

@@ -2,7 +2,7 @@
 
 The library is linked from separate translation units compiled in parallel:
 ``scpqp.hip`` (the C-ABI host side), ``plant.hip``, ``metrics.hip``, ``obstacles.hip``,
-``sensing.hip``, ``estimator.hip``, ``tracker.hip``, ``manoeuvres.hip``, ``tracker_accel.hip``, ``imm.hip``, ``margin.hip``, ``governor.hip``, ``yield.hip``, and
+``sensing.hip``, ``estimator.hip``, ``tracker.hip``, ``manoeuvres.hip``, ``tracker_accel.hip``, ``imm.hip``, ``margin.hip``, ``governor.hip``, ``yield.hip``, ``drive.hip``, and
 ``kernels.hip`` once per kernel group (``-DSCPQP_KGROUP=1..10``: the kernel instantiations of ``scpqp_kernel.h``).
 """
 from __future__ import annotations
@@ -27,7 +27,8 @@ SRCS = [SRC, os.path.join(CSRC, "plant.hip"), os.path.join(CSRC, "metrics.hip"),
         os.path.join(CSRC, "estimator.hip"), os.path.join(CSRC, "tracker.hip"),
         os.path.join(CSRC, "manoeuvres.hip"), os.path.join(CSRC, "tracker_accel.hip"),
         os.path.join(CSRC, "imm.hip"), os.path.join(CSRC, "margin.hip"),
-        os.path.join(CSRC, "governor.hip"), os.path.join(CSRC, "yield.hip")]
+        os.path.join(CSRC, "governor.hip"), os.path.join(CSRC, "yield.hip"),
+        os.path.join(CSRC, "drive.hip")]
 KERNEL_GROUPS = 10
 INCLUDE = os.path.join(_REPO, "include")
 LIB_PATH = os.path.join(_PKG, "libscpqp.so")

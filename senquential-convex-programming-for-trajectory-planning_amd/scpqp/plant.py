@@ -9,6 +9,8 @@
                       integrators, and ``draw_ec_noise`` for the solve's ec_noise
 ``plant_step(..., truth=)``  the plant step with a truth row per (realisation, vehicle)
                       (include/scpqp_truth.h; rows from scpqp/truth.py)
+``plant_step(..., drive=, a_cmd=)``  the same behind a longitudinal actuator per
+                      (realisation, vehicle) (include/scpqp_drive.h; rows from scpqp/drive.py)
 
 Arrays are torch-ROCm float64 tensors on the GPU; PyTorch only provides the
 memory and the stream.  The reference integrates with scipy (odeint / dopri5);
@@ -121,7 +123,7 @@ def delay_compensate(params, x_meas, u_hold, horizon, n_out=DELAY_STEPS, noise=N
 
 
 def plant_step(params, x_start, u_tick, tick, noise=None, h_max=H_MAX, device=None, rng=None,
-               truth=None):
+               truth=None, drive=None, a_cmd=None):
     """x_start [B, nVeh, 6], u_tick [B, nVeh, K] (K = ticks_per_sim + 1) ->
     x_path [B, nVeh, K, 6]: main.py:184-191 (output k integrated from t0 over
     k ticks with the constant control u_tick[..., k]).  ``noise`` / ``rng`` as in
@@ -129,8 +131,15 @@ def plant_step(params, x_start, u_tick, tick, noise=None, h_max=H_MAX, device=No
     every restart of the reference's integrator consumes fresh draws.  ``truth``
     [B, nVeh, 5]: the plant parameters of every (realisation, vehicle)
     (include/scpqp_truth.h; scpqp/truth.py) instead of ``params``' geometry and the
-    nominal steering lag.  delay_compensate takes none: it is the controller's prediction."""
+    nominal steering lag.  delay_compensate takes none: it is the controller's prediction.
+    ``drive`` [B, nVeh, 6] with ``a_cmd`` [B, nVeh]: the longitudinal actuator of every
+    (realisation, vehicle) and the acceleration commanded over the step
+    (include/scpqp_drive.h; scpqp/drive.py); x_start[..., 4] is then the realised
+    acceleration.  One without the other is refused; without ``truth`` the nominal rows are
+    filled in."""
     _one_noise_source(noise, rng)
+    if (drive is None) != (a_cmd is None):
+        raise ValueError("drive and a_cmd go together: pass both or neither")
     device = torch.device(device or "cuda")
     lib = LB.load()
     x = _dev(x_start, device)
@@ -141,6 +150,23 @@ def plant_step(params, x_start, u_tick, tick, noise=None, h_max=H_MAX, device=No
         raise ValueError("x_start must be [B, nVeh, 6] and u_tick [B, nVeh, K]")
     nz = None if noise is None else _dev(noise, device)
     out = torch.empty((B, V, K, 6), dtype=torch.float64, device=device)
+    if drive is not None:
+        from . import truth as TR
+        dr, ac = _dev(drive, device), _dev(a_cmd, device)
+        if tuple(dr.shape) != (B, V, LB.DRIVE_NP) or tuple(ac.shape) != (B, V):
+            raise ValueError("drive must be [B, nVeh, 6] and a_cmd [B, nVeh]")
+        tr = TR.nominal(params, B, device) if truth is None else _dev(truth, device)
+        if tuple(tr.shape) != (B, V, LB.TRUTH_NP):
+            raise ValueError("truth must be [B, nVeh, 5]")
+        if nz is not None and tuple(nz.shape) != (B, V, 2):
+            raise ValueError("noise must be [B, nVeh, 2]")
+        ns = None if rng is None else rng.c_struct()
+        LB.check(lib.scpqp_plant_step_drive(C.byref(params), B, K - 1, float(tick), _ptr(x),
+                                            _ptr(u), _ptr(tr), _ptr(nz),
+                                            None if ns is None else C.byref(ns), _ptr(ac),
+                                            _ptr(dr), _ptr(out), float(h_max),
+                                            _stream(device)), lib)
+        return out
     if truth is not None:
         tr = _dev(truth, device)
         if tuple(tr.shape) != (B, V, LB.TRUTH_NP):

@@ -47,6 +47,9 @@ the cruise speed.
 ``reset(..., right_of_way=)`` puts the governor with ranks and graded braking in its place
 (include/scpqp_yield.h): in a conflict between two vehicles only the outranked one yields, with
 a deceleration sized to stop before the conflict.
+``reset(..., drive=)`` puts a longitudinal actuator per (realisation, vehicle) between that
+command and the plant (include/scpqp_drive.h): gain, offset, limits, a lag and the hold rule,
+none of which the controller or the governor knows.
 """
 from __future__ import annotations
 
@@ -218,6 +221,8 @@ class ClosedLoopBatch:
         self.obst_margin = None
         self.gov_rows = None           # the governor tuning of reset(..., governor=)
         self.yld_rows = None           # the tuning of reset(..., right_of_way=)
+        self.drive_rows = None         # the drive truth of reset(..., drive=)
+        self.a_cmd = None              # with it: the acceleration command in force [B, nVeh]
         self.trace = trace     # keep every step's solve inputs and per-SCP-iteration trace
         self.out = self.solver.alloc_out(self.B, trace=trace)
         self.history = []
@@ -230,7 +235,7 @@ class ClosedLoopBatch:
     def reset(self, x_init, noise=None, seed=None, sigma=PL.SIGMA_NOISE, b_offset=0, truth=None,
               obstacles=None, sensing=None, obstacle_sensing=None, sense_seed=None,
               estimator=None, tracker=None, manoeuvres=None, tracker_accel=None, imm=None,
-              margin=None, governor=None, right_of_way=None):
+              margin=None, governor=None, right_of_way=None, drive=None):
         """main.py:73-75: vehiclePathFullRes[:, v, 0] = x0; the control path holds
         scenario.u0 for the first ticks_delay_u + ticks_per_sim + 1 ticks.
 
@@ -339,7 +344,33 @@ class ClosedLoopBatch:
         with ``governor`` is refused.  The record gains ``accel_cmd``, ``gov_k_conf``,
         ``gov_clear``, ``gov_k_any``, ``gov_who`` and ``gov_d_stop`` [B, nVeh].  Validated here,
         before anything is launched; None, or every row off: nothing is allocated or launched
-        and the rollout is what it was."""
+        and the rollout is what it was.
+
+        ``drive`` [B, nVeh, 6] (scpqp/drive.py; include/scpqp_drive.h): the longitudinal
+        actuator of every (realisation, vehicle).  It needs ``governor=`` or ``right_of_way=``:
+        without one nothing commands the acceleration.  The command then lives in its own
+        tensor ``a_cmd`` [B, nVeh], initialised from ``x_init[:, :, 4]`` and replaced by the
+        governor's output at the end of each step, and ``state[:, :, 4]`` is the realised
+        acceleration, which the governor no longer writes.  The controller side never sees the
+        realised acceleration: column 4 of what the sensor, the estimator and the delay
+        compensation are handed is the command in force from the measured tick on (the new
+        command at the step's first tick, the previous step's inside the previous step),
+        which is what those columns hold without a drive.  The steering limit keeps reading the
+        realised speed.  The record gains ``accel_real`` [B, nVeh], the realised acceleration
+        at the step's end.  Validated here, before anything is launched; None, or every row
+        ideal: nothing is allocated or launched and the rollout is what it was."""
+        if drive is not None:
+            from . import drive as DRV
+            if governor is None and right_of_way is None:
+                raise ValueError("drive needs governor= or right_of_way=: without one nothing "
+                                 "commands the acceleration")
+            dv = drive.detach().cpu().numpy() if isinstance(drive, torch.Tensor) \
+                else np.asarray(drive, float)
+            if tuple(dv.shape) != (self.B, self.nV, DRV.NP):
+                raise ValueError(f"drive must be [B, nVeh, 6] = [{self.B}, {self.nV}, 6]")
+            DRV.validate(dv, self.h_max)
+            if DRV.is_ideal(dv):
+                drive = None
         if right_of_way is not None:
             from . import yielding as YLD
             if governor is not None:
@@ -548,6 +579,18 @@ class ClosedLoopBatch:
             self.yld_rows = torch.as_tensor(right_of_way, dtype=torch.float64,
                                             device=self.device).contiguous().clone()
             self.gov_dreq = YLD.required(self.sc, self.variants, self.variant_of, self.device)
+        self.drive_rows = self.a_cmd = self.drive_truth = None
+        self.state_c = self.last_path_c = None     # the controller's side of state / last_path
+        if drive is not None:
+            self.drive_rows = torch.as_tensor(drive, dtype=torch.float64,
+                                              device=self.device).contiguous().clone()
+            self.a_cmd = x[:, :, 4].clone()
+            self.state_c = x.clone()
+            if self.truth is None:
+                from . import truth as TR
+                self.drive_truth = TR.nominal(self.params, self.B, self.device)
+            else:
+                self.drive_truth = self.truth
         self.last_path = None
         self.u_prev = None
         self.history = []
@@ -655,21 +698,25 @@ class ClosedLoopBatch:
             torch.cuda.synchronize(self.device)
         t_step = time.perf_counter()
         tick_now = i * tps
+        # what the controller's side reads: the realised state and path, with a drive their
+        # copies whose column 4 holds the command in force instead of the realised acceleration
+        state_c = self.state if self.drive_rows is None else self.state_c
+        path_c = self.last_path if self.drive_rows is None else self.last_path_c
         # measured state: tick_now - ticks_delay_x (inside the previous step's path)
-        if self.tdx == 0 or self.last_path is None:
-            x_meas = self.state
+        if self.tdx == 0 or path_c is None:
+            x_meas = state_c
         else:
-            x_meas = self.last_path[:, :, tps - min(self.tdx, tick_now), :].contiguous()
+            x_meas = path_c[:, :, tps - min(self.tdx, tick_now), :].contiguous()
         delivered = None
         if self.sense_rows is not None:
             # the sensing truth: what the controller gets of that tick (include/scpqp_sensing.h)
             from . import sensing as SE
             delivered = torch.empty((B, nV), dtype=torch.int32, device=self.device)
-            if self.last_path is None:
-                x_meas = SE.measure(self.state.contiguous(), 0, self.sense_rows, self.sense_seed, i,
+            if path_c is None:
+                x_meas = SE.measure(state_c.contiguous(), 0, self.sense_rows, self.sense_seed, i,
                                     self.sense_offset, self.x_held, delivered)
             else:
-                x_meas = SE.measure(self.last_path, tps - min(self.tdx, tick_now), self.sense_rows,
+                x_meas = SE.measure(path_c, tps - min(self.tdx, tick_now), self.sense_rows,
                                     self.sense_seed, i, self.sense_offset, self.x_held, delivered)
         x_in, nis = x_meas, None
         if self.est_rows is not None:
@@ -702,7 +749,7 @@ class ClosedLoopBatch:
             # the acceleration in force at tick_now is the governor's own command: with a
             # measurement delay the compensation assumes it over the whole span
             x_plan = x_in.clone()
-            x_plan[:, :, 4] = self.state[:, :, 4]
+            x_plan[:, :, 4] = self.state[:, :, 4] if self.drive_rows is None else self.a_cmd
         x0, dtraj = PL.delay_compensate(self.params, x_plan.contiguous(), u_hold, horizon,
                                         noise=self.noise, h_max=self.h_max, device=self.device,
                                         rng=rng)
@@ -740,8 +787,15 @@ class ClosedLoopBatch:
         timelist = np.linspace(i * sc.dt, (i + 1) * sc.dt, tps + 1)
         idx = [min(self.ticks_total, math.ceil(t / sc.tick_length) + 1) for t in timelist]
         u_tick = self.control[:, :, torch.as_tensor(idx, device=self.device)].contiguous()
-        path = PL.plant_step(self.params, self.state, u_tick, sc.tick_length, noise=self.noise,
-                             h_max=self.h_max, device=self.device, rng=rng, truth=self.truth)
+        x_start = self.state
+        if self.drive_rows is not None:
+            # the drive truth (include/scpqp_drive.h): the command in force over this step
+            path = PL.plant_step(self.params, x_start, u_tick, sc.tick_length, noise=self.noise,
+                                 h_max=self.h_max, device=self.device, rng=rng,
+                                 truth=self.drive_truth, drive=self.drive_rows, a_cmd=self.a_cmd)
+        else:
+            path = PL.plant_step(self.params, x_start, u_tick, sc.tick_length, noise=self.noise,
+                                 h_max=self.h_max, device=self.device, rng=rng, truth=self.truth)
         if self.path_metrics is not None:
             # every global tick once: entry 0 of a later step is the previous step's last
             self.path_metrics.accumulate(path, tick0=i * tps, k_first=0 if i == 0 else 1,
@@ -749,7 +803,16 @@ class ClosedLoopBatch:
                                          manoeuvres=self.man_rows, check_off=False)
         self.last_path = path
         self.state = path[:, :, tps, :].contiguous()
-        if gov is not None:
+        if self.drive_rows is not None:
+            # the controller's copy of the path carries the command that was in force over it,
+            # its copy of the state the command that takes effect at the start of step i + 1
+            self.last_path_c = path.clone()
+            self.last_path_c[:, :, :, 4] = self.a_cmd[:, :, None]
+            if gov is not None:
+                self.a_cmd = gov[0].clone()
+            self.state_c = self.state.clone()
+            self.state_c[:, :, 4] = self.a_cmd
+        elif gov is not None:
             # the command takes effect at the start of step i + 1
             self.state[:, :, 4] = gov[0]
         rec = dict(x0=x0, u0=u_hold, umax=umax, U=U, traj=out.traj.clone(),
@@ -773,6 +836,8 @@ class ClosedLoopBatch:
             rec["accel_cmd"], rec["gov_k_conf"], rec["gov_clear"] = gov[:3]
             if len(gov) > 3:
                 rec["gov_k_any"], rec["gov_who"], rec["gov_d_stop"] = gov[3:]
+        if self.drive_rows is not None:
+            rec["accel_real"] = self.state[:, :, 4].clone()   # realised, at the step's end
         if self.sense_rows is not None:
             rec["x_meas"] = x_meas  # what the controller was told of the vehicles
             rec["delivered"] = delivered

@@ -21,7 +21,8 @@ realisation per spawned single-threaded worker.
                                   [--margin-kappa K [--margin-max M]]
                                   [--govern [--gov-brake A] [--gov-look N] [--gov-band M]
                                    [--gov-prio index|reverse|equal] [--gov-ease A]
-                                   [--gov-stand S]]
+                                   [--gov-stand S]
+                                   [--drive-lag S] [--drive-brake-max A] [--drive-hold]]
 
 Prints one JSON line: realisation-steps/s on the GPU and the CPU, and the
 largest state difference between the two on the CPU sample.  ``--noise-seed S``
@@ -107,6 +108,13 @@ or the same for all (default ``equal``), the gentlest deceleration A m/s^2 (defa
 off).  With any of the three the line adds ``gov_frac_any_conflict`` (a conflict with anybody,
 counted or not), ``gov_frac_yield_to_vehicle`` and ``gov_mean_d_stop``; without them the line is
 what it was.
+``--drive-lag S``, ``--drive-brake-max A`` and ``--drive-hold`` (each needs ``--govern``) put a
+longitudinal actuator between the governor's command and the plant (include/scpqp_drive.h;
+``reset(..., drive=)``): ``drive.rows`` with TAU_A = S seconds, B_MAX = A m/s^2 and HOLD = 1, the
+same row for every (realisation, vehicle), the other fields ideal.  Like the governor it runs in
+every run of the tool.  The line adds ``drive`` (the row), ``drive_mean_accel_gap`` (the mean of
+|realised - commanded| acceleration at the end of the steps) and ``drive_frac_held`` (the share of
+vehicle-steps that end at a speed of exactly zero).
 """
 import json
 import multiprocessing as mp
@@ -320,6 +328,17 @@ def main():
                 raise SystemExit(f"--gov-{key} needs --govern")
     if yld_opt.get("prio", YLD_PRIO) not in ("index", "reverse", "equal"):
         raise SystemExit("--gov-prio takes index, reverse or equal")
+    drive_opt = {}
+    for key, flag in (("tau", "--drive-lag"), ("b_max", "--drive-brake-max")):
+        if flag in argv:
+            at = argv.index(flag)
+            drive_opt[key] = float(argv[at + 1])
+            del argv[at:at + 2]
+    if "--drive-hold" in argv:
+        argv.remove("--drive-hold")
+        drive_opt["hold"] = 1
+    if drive_opt and not govern:
+        raise SystemExit("--drive-lag, --drive-brake-max and --drive-hold need --govern")
     for key in holds:
         if f"--{key}-hold" in argv:
             at = argv.index(f"--{key}-hold")
@@ -434,6 +453,13 @@ def main():
                     s_stand=yld_opt.get("stand", YLD_STAND))
         except ValueError as e:
             raise SystemExit(f"--govern: {e}") from None
+    if drive_opt:
+        from scpqp import drive as DRV
+        try:
+            man_kw["drive"] = DRV.rows(B, sc.nVeh, **drive_opt)
+            DRV.validate(man_kw["drive"], cl.h_max)
+        except ValueError as e:
+            raise SystemExit(f"--drive-*: {e}") from None
     cl.reset(x_init, seed=noise_seed, truth=truth, obstacles=rows, **sense_kw, **est_kw, **trk_kw,
              **man_kw)
     cl.run(1)                      # warm-up (library load, first launches)
@@ -489,6 +515,12 @@ def main():
             fin = ds[torch.isfinite(ds)]
             out["gov_mean_d_stop"] = float(fin.mean().item()) if fin.numel() else None
         out["min_speed"] = float(torch.stack(speeds).min().item())
+        if drive_opt:
+            out["drive"] = dict(zip(DRV.FIELDS, man_kw["drive"][0, 0].tolist()))
+            if "accel_real" in hist[0]:            # an ideal row runs the rollout without a drive
+                real = torch.stack([h["accel_real"] for h in hist])
+                out["drive_mean_accel_gap"] = float((real[1:] - acc[:-1]).abs().mean().item())
+            out["drive_frac_held"] = float((torch.stack(speeds) == 0).float().mean().item())
         out["status_words"] = sorted(set(torch.stack([h["status"] for h in hist]).flatten().tolist()))
     if metrics:
         out["metrics"] = summary

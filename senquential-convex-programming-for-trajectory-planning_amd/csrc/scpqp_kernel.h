@@ -1248,6 +1248,33 @@ __device__ __forceinline__ void assemble_tiles(const cParams& P, const LT& L, PD
     }
 }
 
+// The omega-coupling passes of the assembly (yb, the omega row of H) off its serial path:
+//   * the thread that forms the diagonal block W~_vv,k visits the rows incident to (v, k)
+//     anyway, so it forms yb[(v, k)] from the same loads (plus rowW), in incident_sum's
+//     order and operation form: phase 1 loses its yb items, at c2 its second round;
+//   * where the tile pass is a single round of 4 x 4 tiles on an LDS factor (c2 / c4 210
+//     tiles, c5's Hp-10 class 78), the omega row is formed by the last two waves after
+//     their own tiles (at c2 8 and 4 trips against wave 0's 20) instead of by all four
+//     after the pass: it reads yb and g, which phase 1's barrier published, and writes row
+//     N of H, which no tile touches;
+// Every stored value is bitwise what the order in front gives.  -DSCPQP_DIAG_ASM_FRONT keeps
+// that order (yb as items of its own, the omega row on all four waves behind the tiles): the
+// bitwise reference.  (A third cut, the cold start without its omega work, did not pay in
+// its A/B and is not kept: tools/patches/asm_cold_skip.patch, profiles/asmoverlap_ab_cuts.txt.)
+#ifdef SCPQP_DIAG_ASM_FRONT
+constexpr bool kAsmOverlap = false;
+#else
+constexpr bool kAsmOverlap = true;
+#endif
+// the two cuts, each with an A/B of its own (profiles/asmoverlap_ab_cuts.txt: builds with one
+// of them off and with one of them alone)
+constexpr bool kAsmFuseYb = kAsmOverlap;        // yb beside the diagonal W~ blocks
+constexpr bool kAsmOmegaBeside = kAsmOverlap;   // the omega row beside a single-round tile pass
+constexpr int kAsmOmegaWaves = 2;   // the waves NWAVE - 2, NWAVE - 1 form the omega row
+// tests/asm_overlap_harness.py restates this assignment for tests/test_asm_overlap_host.py
+// (OMEGA_WAVES, omega_beside, tile_decode, split3_outputs' kSplit and kPerWave): a change to
+// kAsmOmegaWaves, to the `beside` condition in assemble() or to those must be made there too.
+
 template <class LT, class PD>
 __device__ void assemble(const cParams& P, const LT& L, PD d, double rho) {
     const int tid = threadIdx.x, V = L.V, Hb = L.Hb, nb = L.nb;
@@ -1255,7 +1282,7 @@ __device__ void assemble(const cParams& P, const LT& L, PD d, double rho) {
     // phase 1: W~ blocks [k][a>=b] (2x2) and the omega-coupling vector in y-space (yb)
     const int nW = Hb * nb;
     PROF_T0_FINE();
-    for (int e = tid; e < nW + V * Hb; e += NT) {
+    for (int e = tid; e < (kAsmFuseYb ? nW : nW + V * Hb); e += NT) {
         if (e < nW) {
             const int k = e / nb, ab = e % nb;
             int a_ = 0;
@@ -1266,6 +1293,10 @@ __device__ void assemble(const cParams& P, const LT& L, PD d, double rho) {
                 const double qk = 2.0 * u2 * ((k == Hb - 1) ? P.Qf[a_] : P.Q[a_]);
                 w00 = qk;
                 w11 = qk;
+                // yb[(a_, k)] beside the block: incident_sum's rows, order, signs and
+                // operation form (c = sign * (d_r w_r), s += c * e), from this loop's loads
+                constexpr bool yb_here = kAsmFuseYb;
+                double s0 = 0.0, s1 = 0.0;
                 for (int wv = 0; wv < V; ++wv) {
                     if (wv == a_) continue;
                     const int i = a_ < wv ? a_ : wv, j = a_ < wv ? wv : a_;
@@ -1274,6 +1305,11 @@ __device__ void assemble(const cParams& P, const LT& L, PD d, double rho) {
                     w00 += dr * e0 * e0;
                     w01 += dr * e0 * e1;
                     w11 += dr * e1 * e1;
+                    if constexpr (yb_here) {
+                        const double c = (a_ == i ? -1.0 : 1.0) * (dr * L.rowW[r]);
+                        s0 += c * e0;
+                        s1 += c * e1;
+                    }
                 }
                 for (int o = 0; o < L.O; ++o) {
                     const int r = L.mp + (a_ * L.O + o) * Hb + k;
@@ -1281,7 +1317,19 @@ __device__ void assemble(const cParams& P, const LT& L, PD d, double rho) {
                     w00 += dr * e0 * e0;
                     w01 += dr * e0 * e1;
                     w11 += dr * e1 * e1;
+                    if constexpr (yb_here) {
+                        const double c = -(dr * L.rowW[r]);
+                        s0 += c * e0;
+                        s1 += c * e1;
+                    }
                 }
+                if constexpr (yb_here) {
+                    const int q = a_ * Hb + k;
+                    L.yb[2 * q] = s0;
+                    L.yb[2 * q + 1] = s1;
+                }
+                (void)s0;
+                (void)s1;
             } else {
                 const int r = pair_index(b_, a_, V) * Hb + k;   // b_ < a_
                 const double e0 = L.rowE[2 * r], e1 = L.rowE[2 * r + 1], dr = -d[r];
@@ -1326,12 +1374,40 @@ __device__ void assemble(const cParams& P, const LT& L, PD d, double rho) {
         assemble_tiles<4>(P, L, d, rho);
 #endif
     }
-    PROF_ACC_FINE0(26);
     const int N = L.N;
-    toeplitz_t_apply(L, L.yb, [&](int e, double tt) { L.H[roff(N) + e] = tt; });
-    if (tid == 0) L.H[roff(N) + N] = red[0] + d[L.mc - 1] + rho;
+    {
+        // the omega row of H.  A single round of tiles on an LDS factor: the last
+        // kAsmOmegaWaves waves, which have few tiles or none, form it after their own
+        // tiles as virtual waves (split3_outputs' w), so every output and every lane of
+        // the three-lane split keeps its place; the other waves skip it.  Multi-round
+        // passes keep all four waves busy, and there the row stays behind the tiles.
+        // (the condition is restated as omega_beside in tests/asm_overlap_harness.py)
+        bool beside = false;
+        if constexpr (kAsmOmegaBeside && !LT::HGLOBAL)
+            beside = V * (T4 * (T4 + 1) / 2) + PV * T4 * T4 <= NT;
+        auto orow = [&](int e, double tt) { L.H[roff(N) + e] = tt; };
+        // (fine stamps are wave 0's: 27 is then its wait at the closing barrier)
+        PROF_ACC_FINE0(26);
+        if (beside) {
+            const int w = __builtin_amdgcn_readfirstlane(tid >> 6) - (NWAVE - kAsmOmegaWaves);
+            for (int vw = w; vw >= 0 && vw < NWAVE; vw += kAsmOmegaWaves) toeplitz_t_apply(L, L.yb, orow, vw);
+        } else {
+            toeplitz_t_apply(L, L.yb, orow);
+        }
+        // red[0]: the ww sum, read after block_reduce4's barrier
+        if (tid == 0) L.H[roff(N) + N] = red[0] + d[L.mc - 1] + rho;
+    }
     bar();
     PROF_ACC_FINE0(27);
+}
+// The cold start's system P + G'G with its omega row decoupled (d = 1, rho = 0): a full
+// assembly, then row N overwritten by e_N and a barrier of its own.
+template <class LT>
+__device__ __forceinline__ void assemble_cold(const cParams& P, const LT& L) {
+    assemble(P, L, L.dd, 0.0);
+    const int N = L.N, o = roff(N);
+    for (int e = threadIdx.x; e <= N; e += NT) L.H[o + e] = e == N ? 1.0 : 0.0;
+    bar();
 }
 
 // ---------------------------------------------------------------------------
@@ -3125,10 +3201,7 @@ PHASE_OVL int ph_assemble_factor(Ctx c, double rho) {
 // (ph_rhs_from_tv at rho = 0; tv = h and dz = 0 from ph_init_a), as in ph_assemble_factor
 PHASE_OVL void ph_init_assemble_factor(Ctx c) {
     LAYDEF;
-    assemble(P, L, L.dd, 0.0);
-    const int N = L.N, o = roff(N);
-    for (int e = threadIdx.x; e <= N; e += NT) L.H[o + e] = e == N ? 1.0 : 0.0;
-    bar();
+    assemble_cold(P, L);
     // P + G'G is positive definite (box and omega rows)
     if constexpr (OVL && FWD) {
         cholesky(L, rhs_from_tv_side(P, L, 0.0), FWD_CALL(0));
